@@ -4,12 +4,22 @@ global batch + gradient all-reduce + LARS step.  Workload = BASELINE.json config
 128-bin x 1024-frame spectrograms, S = 316 tokens); with N GPUs the global batch is 512 * N (configs[3] at N = 8).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full          # + the extra measurements listed below
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR
     python bench.py --gpus N --steps K --warmup W        # starts its own N replicas (child torch.distributed.run, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W           # the driver's form: already under a launcher, runs as one replica
 
-Prints ONE JSON line on rank 0 (contract in the task description): metric/value/unit, roofline of the dominant
-kernel (c_fc forward contraction, timed live with HIP events), cpu_baseline (the CPU oracle on the host cores).
+Prints ONE JSON line on rank 0: metric / value / unit / ms_per_step of the timed steps.  A plain run does nothing else: set-up,
+warm-up, the timed steps, the outputs (--dump-outputs), the line.  With --full the line also carries the roofline of the dominant
+kernel (c_fc forward contraction, timed with HIP events in the timed steps and in a serial post-pass), the InfoNCE group and the
+audio encoder alone, the step with the full last block, and cpu_baseline (the CPU oracle on the host cores); the --no-* options
+switch single ones of these off.
+
+--dump-outputs DIR writes what the last timed step computed, as float32 / float64 .npy files (at most 48 MiB; 18 MB at the headline):
+loss.npy (the loss the step returned), params.npy and grads.npy (a fixed, seeded sample of every trainable parameter after the
+optimizer step and of its gradient, the same elements in both, parameters in name order).  The inputs, the initial weights and
+the sample are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -85,14 +95,19 @@ def parse():
                     help="running.last_block_rows=False: evaluate the towers' last block on every token, as the reference does before "
                          "its read-out discards all rows but one (default: on the read-out rows only -- exact up to rounding order, see DESIGN.md)")
     ap.add_argument("--no-full-last-block-check", action="store_true",
-                    help="skip the 8 extra steps that report the step time with the full last block beside the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-encoder-alone", action="store_true", help="skip the 13 extra audio-encoder-only iterations (profiling runs: the "
+                    help="--full: skip the 8 extra steps that report the step time with the full last block beside the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle's timing")
+    ap.add_argument("--no-encoder-alone", action="store_true", help="--full: skip the 13 extra audio-encoder-only iterations (profiling runs: the "
                     "per-step kernel tables divide by the number of whole steps)")
     ap.add_argument("--script", choices=["va", "at"], default="va",
                     help="va: BASELINE configs[1]/[3] (the headline; frozen image tower).  at: configs[2] -- audio tower + frozen "
                          "CLIP text tower at L=77, local negatives (run_bimodal_at.sh); extra measurement, not the headline")
     ap.add_argument("--cpu-batch", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="also the extra measurements (roofline of the dominant kernel, InfoNCE and audio encoder alone, full last "
+                         "block, CPU baseline); a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and a seeded sample of the updated parameters and their gradients to DIR/*.npy")
     ap.add_argument("--comm-overlap", choices=["block", "step"], default="block",
                     help="running.comm_overlap: replicas reduce each block's gradient bucket while the blocks below run their backward "
                          "(block, default) or all buckets as one collective after the backward (step)")
@@ -214,6 +229,32 @@ def cpu_baseline(args, T, Fq):
                      "median_step_s": round(t_cfg1, 3), "pairs_per_s": round(b1 / t_cfg1, 2)}}
 
 
+DUMP_ELEMENTS = 6 << 20        # elements per sampled array of --dump-outputs (float32): params.npy + grads.npy <= 48 MiB
+
+
+def dump_outputs(path, model, loss):
+    """What the last timed step gave its caller, as <path>/<name>.npy: the loss it returned (float64), the trainable parameters
+    after its optimizer step and the gradients it left on them (float32).  Parameters and gradients are a fixed sample of the same
+    elements: parameters in name order, each one whole when it is smaller than an equal share of DUMP_ELEMENTS, else that share at
+    seeded positions (sorted)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    named = [(k, p) for k, p in model.named_parameters() if p.requires_grad]
+    share = DUMP_ELEMENTS // max(len(named), 1)
+    gen = torch.Generator().manual_seed(0)
+    vals, grads = [], []
+    for _, p in named:
+        flat = p.detach().reshape(-1)
+        n = flat.numel()
+        idx = torch.arange(n) if n <= share else torch.randint(0, n, (share,), generator=gen).sort().values
+        idx = idx.to(flat.device)
+        vals.append(flat[idx].float())
+        grads.append(p.grad.detach().reshape(-1)[idx].float() if p.grad is not None else torch.zeros(idx.numel(), device=flat.device))
+    np.save(os.path.join(path, "loss.npy"), np.array([float(loss.detach())], dtype=np.float64))
+    np.save(os.path.join(path, "params.npy"), torch.cat(vals).cpu().numpy())
+    np.save(os.path.join(path, "grads.npy"), torch.cat(grads).cpu().numpy())
+
+
 def bench_at(args, world, rank, local_rank, dev, use_dist):
     """AT fine-tuning step (BASELINE configs[2]): trainable audio head, frozen causal text tower, VALCELossHead(al)."""
     from vipant_amd import _ffi
@@ -262,6 +303,8 @@ def bench_at(args, world, rank, local_rank, dev, use_dist):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
     ms = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mon.model, loss)
     S = mon.model.audio_head.misc.positional_embedding.shape[0]
     # algorithmic work of the step (recomputation and the micro-batch pre-pass are NOT counted as work done)
     lbr = not args.full_last_block
@@ -350,11 +393,12 @@ def main():
 
     for i in range(args.warmup):
         one_step(i)
-    # live per-launch timing of the dominant kernel: c_fc forward contraction (EPI_QUICKGELU_D8), M = b*S, N = 4D, K = D
     S = mon.model.audio_head.misc.positional_embedding.shape[0]
     Mrows = b * S
     W = args.width
-    ops.KERNEL_PROBE["gemm_nt"] = {"events": [], "match": lambda epi, M, N, K: epi == ops.EPI_QUICKGELU_D8 and M == Mrows}
+    if args.full:
+        # live per-launch timing of the dominant kernel: c_fc forward contraction (EPI_QUICKGELU_D8), M = b*S, N = 4D, K = D
+        ops.KERNEL_PROBE["gemm_nt"] = {"events": [], "match": lambda epi, M, N, K: epi == ops.EPI_QUICKGELU_D8 and M == Mrows}
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -365,33 +409,36 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    events = ops.KERNEL_PROBE.pop("gemm_nt")["events"]
+    events = ops.KERNEL_PROBE.pop("gemm_nt")["events"] if args.full else []
     if use_dist:
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
     ms = dt / args.steps * 1e3
-    live_ms = sum(e0.elapsed_time(e1) for e0, e1 in events) / max(len(events), 1)
-    # The roofline figure of the dominant kernel comes from a short SERIAL post-pass (outside the timed region): the same step with the
-    # frozen image tower on the main stream, so that the HIP events around a c_fc launch bracket that launch and nothing else -- the
-    # condition the committed rocprofv3 per-shape tables are taken under (profiles/*_kernel_shapes_serial.txt).  In the timed steps
-    # the image tower's launches on the side stream share the chip with the bracketed launch: that number stays as `in_step_*`.
-    overlap_was = os.environ.get("VIPANT_TOWER_OVERLAP")
-    os.environ["VIPANT_TOWER_OVERLAP"] = "0"
-    ops.KERNEL_PROBE["gemm_nt"] = {"events": [], "match": lambda epi, M, N, K: epi == ops.EPI_QUICKGELU_D8 and M == Mrows}
-    for i in range(3):
-        one_step(args.warmup + args.steps + i)
-    torch.cuda.synchronize()
-    serial_events = ops.KERNEL_PROBE.pop("gemm_nt")["events"]
-    if overlap_was is None:
-        del os.environ["VIPANT_TOWER_OVERLAP"]
-    else:
-        os.environ["VIPANT_TOWER_OVERLAP"] = overlap_was
-    serial_events = serial_events[len(serial_events) // 3:]          # the first of the three steps settles clocks and caches
-    kern_ms = sum(e0.elapsed_time(e1) for e0, e1 in serial_events) / max(len(serial_events), 1)
-    kern_flops = 2.0 * Mrows * (4 * W) * W
-    achieved = kern_flops / (kern_ms * 1e-3) / 1e12 if kern_ms > 0 else 0.0
-    live = kern_flops / (live_ms * 1e-3) / 1e12 if live_ms > 0 else 0.0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mon.model, loss)
+    if args.full:
+        live_ms = sum(e0.elapsed_time(e1) for e0, e1 in events) / max(len(events), 1)
+        # The roofline figure of the dominant kernel comes from a short SERIAL post-pass (outside the timed region): the same step with
+        # the frozen image tower on the main stream, so that the HIP events around a c_fc launch bracket that launch and nothing else --
+        # the condition the committed rocprofv3 per-shape tables are taken under (profiles/*_kernel_shapes_serial.txt).  In the timed
+        # steps the image tower's launches on the side stream share the chip with the bracketed launch: that number stays as `in_step_*`.
+        overlap_was = os.environ.get("VIPANT_TOWER_OVERLAP")
+        os.environ["VIPANT_TOWER_OVERLAP"] = "0"
+        ops.KERNEL_PROBE["gemm_nt"] = {"events": [], "match": lambda epi, M, N, K: epi == ops.EPI_QUICKGELU_D8 and M == Mrows}
+        for i in range(3):
+            one_step(args.warmup + args.steps + i)
+        torch.cuda.synchronize()
+        serial_events = ops.KERNEL_PROBE.pop("gemm_nt")["events"]
+        if overlap_was is None:
+            del os.environ["VIPANT_TOWER_OVERLAP"]
+        else:
+            os.environ["VIPANT_TOWER_OVERLAP"] = overlap_was
+        serial_events = serial_events[len(serial_events) // 3:]          # the first of the three steps settles clocks and caches
+        kern_ms = sum(e0.elapsed_time(e1) for e0, e1 in serial_events) / max(len(serial_events), 1)
+        kern_flops = 2.0 * Mrows * (4 * W) * W
+        achieved = kern_flops / (kern_ms * 1e-3) / 1e12 if kern_ms > 0 else 0.0
+        live = kern_flops / (live_ms * 1e-3) / 1e12 if live_ms > 0 else 0.0
     P = S - 1
     lbr = not args.full_last_block
     step_flops = b * (3 * tower_fwd_flops(S, 1024, P, width=W, layers=args.layers, last_block_rows=lbr)
@@ -412,16 +459,17 @@ def main():
         "loss": round(float(loss.detach()), 4),
         "step_tflops": round(step_flops / (ms * 1e-3) / 1e12, 1),
         "step_mfma_frac": round(step_flops / (ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
-        "roofline": {"bound": "mfma", "kernel": "%s (c_fc forward + QuickGELU, M=%d N=%d K=%d)" % (DOMINANT_KERNEL, Mrows, 4 * W, W),
-                     "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": pmc_traffic(Mrows, 4 * W, W), "traffic_source": PMC_FILE,
-                     "algorithmic_flops": kern_flops, "algorithmic_bytes": 2.0 * (Mrows * W + 4 * W * W) + 3.0 * Mrows * 4 * W,
-                     "launches_timed": len(serial_events), "avg_launch_ms": round(kern_ms, 4),
-                     "timing": "HIP events around each launch in a serial post-pass (image tower on the main stream, 2 of 3 extra steps)",
-                     "in_step_avg_launch_ms": round(live_ms, 4), "in_step_frac": round(live / PEAK_BF16_TFLOPS, 4),
-                     "in_step_launches_timed": len(events)},
     }
-    if rank == 0:
+    if args.full:
+        out["roofline"] = {"bound": "mfma", "kernel": "%s (c_fc forward + QuickGELU, M=%d N=%d K=%d)" % (DOMINANT_KERNEL, Mrows, 4 * W, W),
+                           "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                           "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": pmc_traffic(Mrows, 4 * W, W), "traffic_source": PMC_FILE,
+                           "algorithmic_flops": kern_flops, "algorithmic_bytes": 2.0 * (Mrows * W + 4 * W * W) + 3.0 * Mrows * 4 * W,
+                           "launches_timed": len(serial_events), "avg_launch_ms": round(kern_ms, 4),
+                           "timing": "HIP events around each launch in a serial post-pass (image tower on the main stream, 2 of 3 extra steps)",
+                           "in_step_avg_launch_ms": round(live_ms, 4), "in_step_frac": round(live / PEAK_BF16_TFLOPS, 4),
+                           "in_step_launches_timed": len(events)}
+    if rank == 0 and args.full:
         # the InfoNCE kernel group alone (loss + all three gradients) at the 8-GPU global batch B = 4096
         Bn = 4096
         x1 = torch.nn.functional.normalize(torch.randn(Bn, E, device=dev), dim=-1).requires_grad_()
@@ -513,6 +561,7 @@ def main():
                                       "note": "running.last_block_rows=False: the discarded rows of the last block computed too"}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, T, Fq)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

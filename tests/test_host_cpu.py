@@ -259,3 +259,37 @@ def test_bench_flop_count_follows_the_last_block_form(monkeypatch):
     # a width or a length the folded kernels do not take is counted in the round-3 form
     assert bench.tower_fwd_flops(2000, 1024, 1999, width=D, layers=2, last_block_rows=True) == \
         S * 0 + (2 - 1) * 2000 * (24 * D * D + 4 * 2000 * D) + (4 * 2000 * D * D + 20 * D * D + 4 * 2000 * D) + 2 * 1999 * 1024 * D + 2 * D * 512
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: loss (float64), parameters and gradients (float32) of the trainable parameters only, the same
+    seeded elements from run to run and in both arrays, small parameters whole, at most DUMP_ELEMENTS per array."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.torch = torch
+    monkeypatch.setattr(bench, "DUMP_ELEMENTS", 3000)
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(700, 900), torch.nn.LayerNorm(900), torch.nn.Linear(900, 5))
+    net[1].weight.requires_grad_(False)
+    loss = net(torch.randn(4, 700)).square().mean()
+    loss.backward()
+    dumps = []
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), net, loss)
+        dumps.append({n[:-4]: np.load(tmp_path / tag / n) for n in sorted(os.listdir(tmp_path / tag))})
+    a, b = dumps
+    assert sorted(a) == ["grads", "loss", "params"]
+    assert a["loss"].dtype == np.float64 and a["loss"].shape == (1,) and a["loss"][0] == float(loss)
+    assert a["params"].dtype == a["grads"].dtype == np.float32 and a["params"].shape == a["grads"].shape
+    share = 3000 // 5                        # five trainable tensors (900 x 700, 900, LN bias 900, 5 x 900, 5): the last one whole
+    assert a["params"].size == 4 * share + 5 <= 3000
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    # the first parameter's sample: seeded positions, sorted, the gradient read at the same ones
+    pos = torch.randint(0, 900 * 700, (share,), generator=torch.Generator().manual_seed(0)).sort().values.numpy()
+    assert np.array_equal(a["params"][:share], net[0].weight.detach().reshape(-1).numpy()[pos])
+    assert np.array_equal(a["grads"][:share], net[0].weight.grad.reshape(-1).numpy()[pos])
+    assert np.array_equal(a["params"][-5:], net[2].bias.detach().numpy()) and np.array_equal(a["grads"][-5:], net[2].bias.grad.numpy())
