@@ -350,6 +350,36 @@ int32_t vipant_lars_step(float* const* p, const float* const* g, float* const* m
                          const int32_t* adapt, const float* lr, int64_t ntensors, float weight_decay,
                          float momentum, float eta, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Barlow Twins loss head (BarlowLossHead, cvap/module/decoder/loss_head.py:287-328) -----------------------------------
+ * Batch normalisation over the batch dimension (torch.nn.BatchNorm1d, training mode, loss_head.py:296-303, 313): x fp32 [M, N]
+ * (row stride ldx) -> y bf16 [M, N] (row stride N) = [ReLU]((x - mean) * rstd [* gamma + beta]); mean / rstd fp32 [N] are the
+ * biased batch statistics, saved for the backward.  gamma / beta (fp32 [N]) both NULL = affine=False; relu != 0 fuses the
+ * projector's ReLU.  running_mean / running_var (optional, fp32 [N]) are updated in the same launches with `momentum` and the
+ * unbiased variance; num_batches_tracked (optional, int64 [1]) is incremented.  M >= 2 (VIPANT_EBADSHAPE otherwise, as torch
+ * refuses a one-row batch in training).  Deterministic: the column reductions are two-level through `workspace`
+ * (vipant_batchnorm_workspace_bytes), no float atomics. */
+size_t vipant_batchnorm_workspace_bytes(int64_t M, int64_t N);
+int32_t vipant_batchnorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta, int32_t relu, uint16_t* y,
+                             float* mean, float* rstd, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                             float momentum, float eps, int64_t M, int64_t N, void* workspace, size_t workspace_bytes,
+                             void* stream);
+/* dx bf16 [M, N] (row stride N) from dy fp32 [M, N] (row stride lddy, the gradient of the normalised [and rectified] output) and
+ * the saved pre-normalisation x, mean, rstd; the ReLU mask is recomputed from x, gamma, beta.  The column sums dx needs run over
+ * all M rows; dgamma / dbeta (fp32 [N], optional, (+)= with accumulate) are summed over rows [row0, row0 + nrows) only -- the
+ * rows a replica owns.  Same workspace as the forward. */
+int32_t vipant_batchnorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* mean, const float* rstd,
+                             const float* gamma, const float* beta, int32_t relu, uint16_t* dx, float* dgamma, float* dbeta,
+                             int64_t row0, int64_t nrows, int32_t accumulate, int64_t M, int64_t N, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* The cross-correlation loss (loss_head.py:305-311, 318-327): c fp32 [N, N] = zn1^T zn2 un-scaled (vipant_gemm_tn over the batch,
+ * K = M); the kernel applies 1 / M.  loss fp32 [3] = {on + lambd * off, on, off}, on = sum_i (c_ii - 1)^2, off = sum_{i != j} c_ij^2.
+ * G / Gt (optional, together, bf16 [N, N]) receive g = d loss / d c * (1 / M) * grad_scale[0] (grad_scale: optional device fp32
+ * scalar, the upstream gradient) and its transpose: dzn1 = zn2 . G^T and dzn2 = zn1 . G are two vipant_gemm_nt calls (B = G, Gt).
+ * Deterministic two-level reduction through `workspace` (vipant_barlow_loss_workspace_bytes). */
+size_t vipant_barlow_loss_workspace_bytes(int64_t N);
+int32_t vipant_barlow_loss(const float* c, int64_t ldc, int64_t M, float lambd, float* loss, const float* grad_scale, uint16_t* G,
+                           uint16_t* Gt, int64_t N, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ==== The fused operator set: one entry point per reference operator group, forward and backward ==========
  * Host-side compositions of the kernels above (vipant_amd/csrc/block.hip): same stream, no allocation, no synchronisation.
  * Fusion plan: a residual add rides on the NEXT LayerNorm pass (`add` bf16 [M,D] = the previous branch output, `x_out` fp32

@@ -124,6 +124,12 @@ PROTOTYPES = {
     "vipant_eot_ln_proj_l2norm_fwd": (_i32, [_p] * 12 + [_i64] * 4 + [_i32, _p]),
     "vipant_lars_workspace_bytes": (_sz, [_i64]),
     "vipant_lars_step": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _f32, _f32, _f32, _p, _sz, _p]),
+    # Barlow Twins loss head (vipant_amd/csrc/barlow.hip)
+    "vipant_batchnorm_workspace_bytes": (_sz, [_i64, _i64]),
+    "vipant_batchnorm_fwd": (_i32, [_p, _i64, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _f32, _f32, _i64, _i64, _p, _sz, _p]),
+    "vipant_batchnorm_bwd": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _p, _i32, _p, _p, _p, _i64, _i64, _i32, _i64, _i64, _p, _sz, _p]),
+    "vipant_barlow_loss_workspace_bytes": (_sz, [_i64]),
+    "vipant_barlow_loss": (_i32, [_p, _i64, _i64, _f32, _p, _p, _p, _p, _i64, _p, _sz, _p]),
 }
 
 

@@ -90,6 +90,12 @@ GROUPS = {
         "ce": {"name": "CELossHead", "layers": [], "scaling": True, "scale_max": None},
         "ce_val": {"name": "VALCELossHead", "layers": [], "scaling": True, "scale_max": None,
                    "va": True, "lv": False, "al": True},
+        "barlow": {"name": "BarlowLossHead", "embed_dim": "${model.image.embed_dim}", "lambd_off": 0.0051,
+                   "layers": [2048, 4096, 4096]},
+        # `ce` carries only `name`, as in the reference's file: BarlowCELossHead fills scaling / scale_max from `ce` (logged)
+        "barlow_ce": {"name": "BarlowCELossHead", "lambd_barlow": 0.05, "ce": {"name": "CELossHead"},
+                      "barlow": {"name": "BarlowLossHead", "embed_dim": "${model.image.embed_dim}", "lambd_off": 0.0051,
+                                 "layers": [2048, 4096, 4096]}},
     },
     "optimizer": {
         "standard": {

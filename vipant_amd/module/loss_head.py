@@ -7,7 +7,9 @@ Eval path: `infer` caches normalised features on the device, `report` ranks them
 """
 from __future__ import annotations
 
+import copy
 import json
+import logging
 from collections import defaultdict
 
 import numpy as np
@@ -16,6 +18,7 @@ import torch.distributed as dist
 from torch import nn
 
 from .. import ops, parallel
+from .._ffi import VipantError
 from ..registry import Registry
 
 LOSS_HEADS_REGISTRY = Registry("LOSS_HEADS")
@@ -268,6 +271,111 @@ class VALCELossHead(LossHead):
                 self._total_loss[key] += term.detach()
                 loss = loss + term
         return loss
+
+
+def _need_image_features(head, x1):
+    if x1 is None:
+        raise VipantError(f"{head}: the Barlow heads need image features (x1); with dummy images (the AT script, "
+                          "running.imagine / frame_emb) there are none -- model/loss=barlow and barlow_ce are VA-only")
+
+
+@LOSS_HEADS_REGISTRY.register()
+class BarlowLossHead(LossHead):
+    """Barlow Twins objective (cvap/module/decoder/loss_head.py:287-328): a projector of bias-free Linears with BatchNorm1d + ReLU
+    between them, an affine-free BatchNorm1d, and sum_i (c_ii - 1)^2 + lambd_off sum_{i != j} c_ij^2 of the cross-correlation
+    c = bn(z1)^T bn(z2) / B.  Modules and names are the reference's (the state dict loads strictly); the arithmetic of the
+    training forward and backward is ops.BarlowFn (HIP batch norm, loss kernel, the library's contractions).  Eval mode caches
+    features for the retrieval report (LossHead.infer), as the reference does."""
+
+    def __init__(self, cfg, **kwargs):
+        super().__init__()
+        self.normalized = False
+        sizes = [int(cfg.embed_dim)] + [int(w) for w in cfg.layers]
+        if len(sizes) < 2:
+            raise VipantError("BarlowLossHead: `layers` needs at least one width (the projector's output)")
+        for name, w in [("embed_dim", sizes[0])] + [(f"layers[{i}]", v) for i, v in enumerate(sizes[1:])]:
+            if w <= 0 or w % 64:
+                raise VipantError(f"BarlowLossHead: {name} = {w} is not a positive multiple of 64 (the projector's contractions "
+                                  "need K % 64 == 0)")
+        if kwargs.get("negatives", "global") != "global":
+            raise VipantError(f"BarlowLossHead: negatives={kwargs.get('negatives')!r} is not built; the Barlow heads use global "
+                              "negatives (every replica scores the all-gathered batch)")
+        layers = []
+        for i in range(len(sizes) - 2):
+            layers.extend([nn.Linear(sizes[i], sizes[i + 1], bias=False), nn.BatchNorm1d(sizes[i + 1]), nn.ReLU(inplace=True)])
+        layers.append(nn.Linear(sizes[-2], sizes[-1], bias=False))
+        self.linear = nn.Sequential(*layers)
+        self.bn = nn.BatchNorm1d(sizes[-1], affine=False)
+        if any(m.momentum is None for m in self.modules() if isinstance(m, nn.BatchNorm1d)):
+            raise VipantError("BarlowLossHead: BatchNorm1d(momentum=None) is not supported")
+        self.lambd_off = float(cfg.lambd_off)
+        self.reduce = True
+        self.parts = None            # fp32 [3] device tensor of the last training forward: loss, on-diagonal, off-diagonal
+
+    def _projector(self):
+        mods = list(self.linear)
+        lins = [m for m in mods if isinstance(m, nn.Linear)]
+        bns = [m for m in mods if isinstance(m, nn.BatchNorm1d)]
+        params = []
+        for lin, bn in zip(lins[:-1], bns):
+            params += [lin.weight, bn.weight, bn.bias]
+        params.append(lins[-1].weight)
+        return bns, params
+
+    def forward(self, x1, x2, *args, **kwargs):
+        if not self.training:
+            if not dist.is_initialized() or dist.get_rank() == 0:
+                return self.infer(x1, x2, *args, **kwargs)
+            return None
+        _need_image_features(type(self).__name__, x1)
+        b = x1.shape[0]
+        row0 = 0
+        want_dx1 = x1.requires_grad
+        if parallel.active():
+            x1, x2 = parallel.all_gather_features(x1, x2)
+            row0 = parallel.rank() * b
+        bns, params = self._projector()
+        meta = ops.BarlowMeta(bns, self.bn, self.lambd_off, row0, b, want_dx1=want_dx1)
+        loss = ops.BarlowFn.apply(x1.contiguous(), x2.contiguous(), meta, *params)
+        self.parts = meta.parts
+        return loss
+
+
+@LOSS_HEADS_REGISTRY.register()
+class BarlowCELossHead(LossHead):
+    """InfoNCE + lambd_barlow x Barlow Twins (cvap/module/decoder/loss_head.py:601-622); sub-heads `loss_ce` and `loss_barlow`.
+    Eval mode and the report are the InfoNCE head's."""
+
+    CE_DEFAULTS = {"layers": [], "scaling": True, "scale_max": None}     # configs/model/loss/ce.yaml
+
+    def __init__(self, cfg, **kwargs):
+        super().__init__()
+        self.normalized = False
+        ce_cfg = copy.deepcopy(cfg.ce)
+        filled = [k for k in self.CE_DEFAULTS if k not in ce_cfg]
+        for k in filled:
+            ce_cfg[k] = copy.deepcopy(self.CE_DEFAULTS[k])
+        if filled and parallel.rank() == 0:
+            # barlow_ce.yaml's `ce` group names the head only; CELossHead reads cfg.scaling (a KeyError under Hydra's struct mode)
+            logging.getLogger(__name__).warning("BarlowCELossHead: `ce` sub-config has no %s; filled from model/loss=ce (%s)",
+                                                ", ".join(filled), ", ".join(f"{k}={ce_cfg[k]}" for k in filled))
+        self.loss_ce = build_loss_head(ce_cfg, **kwargs)
+        self.loss_barlow = build_loss_head(cfg.barlow, **kwargs)
+        self.lambd_barlow = float(cfg.lambd_barlow)
+        self.reduce = True
+
+    def report(self, gold_file=None):
+        return self.loss_ce.report(gold_file=gold_file)
+
+    def forward(self, x1, x2, *args, **kwargs):
+        if not self.training:
+            if not dist.is_initialized() or dist.get_rank() == 0:
+                return self.loss_ce.infer(x1, x2, *args, **kwargs)
+            return None
+        _need_image_features(type(self).__name__, x1)
+        loss_ce = self.loss_ce(x1, x2, *args, **kwargs)
+        loss_barlow = self.loss_barlow(x1, x2, *args, **kwargs)
+        return loss_ce + self.lambd_barlow * loss_barlow
 
 
 class DummyLossHead(nn.Module):

@@ -1228,3 +1228,163 @@ class LarsState:
         call("vipant_lars_step", self.p_ptrs.data_ptr(), self.g_ptrs.data_ptr(), self.mu_ptrs.data_ptr(), self.n.data_ptr(),
              self.adapt.data_ptr(), self.lr.data_ptr(), len(self.params), float(weight_decay), float(momentum), float(eta),
              self.ws.data_ptr(), self.ws.numel(), _stream())
+
+
+# ---------------------------------------------------------------------------------- Barlow Twins head
+def batchnorm_fwd(x: torch.Tensor, gamma=None, beta=None, *, relu: bool = False, running_mean=None, running_var=None,
+                  num_batches_tracked=None, momentum: float = 0.1, eps: float = 1e-5):
+    """nn.BatchNorm1d in training mode over the rows of x (fp32 [M, N]) [+ ReLU] -> (y bf16 [M, N], mean, rstd fp32 [N]).
+    The running statistics (optional buffers) are updated in the same launches."""
+    _need(x, F32, "batchnorm_fwd.x")
+    M, N = x.shape
+    y = torch.empty((M, N), dtype=BF16, device=x.device)
+    mean = torch.empty((N,), dtype=F32, device=x.device)
+    rstd = torch.empty((N,), dtype=F32, device=x.device)
+    ws = scratch("batchnorm", query("vipant_batchnorm_workspace_bytes", M, N), x.device)
+    call("vipant_batchnorm_fwd", x.data_ptr(), x.stride(0), _ptr(gamma), _ptr(beta), int(relu), y.data_ptr(), mean.data_ptr(),
+         rstd.data_ptr(), _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked), float(momentum), float(eps), M, N,
+         ws.data_ptr(), ws.numel(), _stream())
+    return y, mean, rstd
+
+
+def batchnorm_bwd(dy: torch.Tensor, x: torch.Tensor, mean, rstd, gamma=None, beta=None, *, relu: bool = False, dgamma=None,
+                  dbeta=None, row0: int = 0, nrows: Optional[int] = None, accumulate: bool = False) -> torch.Tensor:
+    """dx bf16 [M, N] of batchnorm_fwd from dy fp32 [M, N]; dgamma / dbeta (+)= their sums over rows [row0, row0 + nrows)."""
+    _need(dy, F32, "batchnorm_bwd.dy"); _need(x, F32, "batchnorm_bwd.x")
+    M, N = x.shape
+    nrows = M - row0 if nrows is None else nrows
+    dx = torch.empty((M, N), dtype=BF16, device=x.device)
+    ws = scratch("batchnorm", query("vipant_batchnorm_workspace_bytes", M, N), x.device)
+    call("vipant_batchnorm_bwd", dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), mean.data_ptr(), rstd.data_ptr(),
+         _ptr(gamma), _ptr(beta), int(relu), dx.data_ptr(), _ptr(dgamma), _ptr(dbeta), int(row0), int(nrows), int(accumulate),
+         M, N, ws.data_ptr(), ws.numel(), _stream())
+    return dx
+
+
+def barlow_loss(c: torch.Tensor, M: int, lambd: float, *, grad_scale: Optional[torch.Tensor] = None, want_grad: bool = False):
+    """Cross-correlation loss of c fp32 [N, N] = zn1^T zn2 (un-scaled, M rows) -> (fp32 [3] = loss, on, off; G; G^T).
+    G = d loss / d c * grad_scale / M in bf16 (None unless want_grad); grad_scale: device fp32 scalar (the upstream gradient)."""
+    _need(c, F32, "barlow_loss.c")
+    N = c.shape[0]
+    assert c.shape == (N, N), c.shape
+    out = torch.empty((3,), dtype=F32, device=c.device)
+    G = torch.empty((N, N), dtype=BF16, device=c.device) if want_grad else None
+    Gt = torch.empty((N, N), dtype=BF16, device=c.device) if want_grad else None
+    if grad_scale is not None:
+        _need(grad_scale, F32, "barlow_loss.grad_scale")
+    ws = scratch("barlow_loss", query("vipant_barlow_loss_workspace_bytes", N), c.device)
+    call("vipant_barlow_loss", c.data_ptr(), c.stride(0), int(M), float(lambd), out.data_ptr(), _ptr(grad_scale), _ptr(G), _ptr(Gt),
+         N, ws.data_ptr(), ws.numel(), _stream())
+    return out, G, Gt
+
+
+def linear_nobias(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """fp32 y [M, out] = x bf16 [M, in] . w^T (nn.Linear(bias=False)), w through cached_bf16."""
+    y = torch.empty((x.shape[0], w.shape[0]), dtype=F32, device=x.device)
+    return gemm_nt(x, cached_bf16(w), y, epi=EPI_F32)
+
+
+class BarlowMeta:
+    """What BarlowFn needs besides its differentiable inputs: the BN modules (running-statistics buffers, momentum, eps), the
+    off-diagonal weight and the rows this replica owns.  `parts` receives the fp32 [3] loss buffer of the last forward."""
+
+    def __init__(self, bns, final_bn, lambd: float, row0: int, nrows: int, want_dx1: bool = True):
+        self.bns, self.final_bn, self.lambd, self.row0, self.nrows = list(bns), final_bn, float(lambd), int(row0), int(nrows)
+        # whether the caller's view-1 features need a gradient: under replicas x1 reaches BarlowFn through the joint feature
+        # all-gather (cat with x2), so `needs_input_grad[0]` is True even for frozen image features
+        self.want_dx1 = bool(want_dx1)
+        self.parts = None
+
+
+def _bn_state(bn):
+    if bn.momentum is None:
+        # torch's cumulative moving average (momentum 1 / num_batches_tracked) is not implemented by the kernel
+        raise _ffi.VipantError("BarlowFn: BatchNorm1d(momentum=None) (cumulative moving average) is not supported")
+    if not bn.training or not bn.track_running_stats:
+        return dict(momentum=bn.momentum, eps=bn.eps)
+    return dict(running_mean=bn.running_mean, running_var=bn.running_var, num_batches_tracked=bn.num_batches_tracked,
+                momentum=bn.momentum, eps=bn.eps)
+
+
+class BarlowFn(torch.autograd.Function):
+    """BarlowLossHead.forward (cvap/module/decoder/loss_head.py:313-328) in training mode as ONE autograd node.
+
+    x1, x2: fp32 [M, E] un-normalised features (the all-gathered global batch under replicas).  params = (W_0, gamma_0, beta_0,
+    ..., W_{L-1}, gamma_{L-1}, beta_{L-1}, W_L): per hidden width a bias-free Linear + BatchNorm1d + ReLU, then the last Linear
+    and the affine-free BatchNorm1d.  Both views go through the same weights, view 1 first, so every BN updates its running
+    statistics twice.  Feature gradients are produced for rows [row0, row0 + nrows) only (zeros elsewhere; their owners compute
+    them), parameter gradients over all M rows -- complete on every replica, like logit_scale's (Barlow head).
+
+    One node rather than one per layer: the tensors between the layers are bf16 forward / fp32 backward (BN output is the next
+    contraction's bf16 operand, its gradient the fp32 product of a contraction), and autograd would cast every such gradient
+    to the forward dtype through ATen."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, meta, *params):
+        _need(x1, F32, "barlow.x1"); _need(x2, F32, "barlow.x2")
+        L = len(meta.bns)
+        Ws, gs, bs = [params[3 * i] for i in range(L)] + [params[3 * L]], [params[3 * i + 1] for i in range(L)], \
+            [params[3 * i + 2] for i in range(L)]
+        M = x1.shape[0]
+        views = []
+        for x in (x1, x2):
+            h = cast_bf16(x.contiguous())[0]
+            hs, ys, st = [h], [], []
+            for i in range(L):
+                y = linear_nobias(h, Ws[i])
+                h, mean, rstd = batchnorm_fwd(y, gs[i], bs[i], relu=True, **_bn_state(meta.bns[i]))
+                ys.append(y); st.append((mean, rstd)); hs.append(h)
+            z = linear_nobias(h, Ws[L])
+            zn, mean, rstd = batchnorm_fwd(z, **_bn_state(meta.final_bn))
+            views.append((hs, ys, st, z, zn, (mean, rstd)))
+        zn1, zn2 = views[0][4], views[1][4]
+        N = zn1.shape[1]
+        c = gemm_tn(zn1, zn2, torch.empty((N, N), dtype=F32, device=x1.device))
+        loss, _, _ = barlow_loss(c, M, meta.lambd)
+        meta.parts = loss
+        ctx.meta, ctx.views, ctx.c, ctx.shapes, ctx.weights = meta, views, c, (M, x1.shape[1]), (Ws, gs, bs)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        meta, views, c = ctx.meta, ctx.views, ctx.c
+        M, E = ctx.shapes
+        L = len(meta.bns)
+        need = (ctx.needs_input_grad[0] and meta.want_dx1,) + tuple(ctx.needs_input_grad[1:])
+        dev = c.device
+        N = c.shape[0]
+        _, G, Gt = barlow_loss(c, M, meta.lambd, grad_scale=dloss.detach().reshape(1).to(F32).contiguous(), want_grad=True)
+        dzn = [gemm_nt(views[1][4], G, torch.empty((M, N), dtype=F32, device=dev), epi=EPI_F32),     # dzn1 = zn2 . G^T
+               gemm_nt(views[0][4], Gt, torch.empty((M, N), dtype=F32, device=dev), epi=EPI_F32)]    # dzn2 = zn1 . G
+        del ctx.c
+        Ws, gs, bs = ctx.weights
+        dW = [torch.empty(w.shape, dtype=F32, device=dev) for w in Ws]
+        dg = [torch.empty(g.shape, dtype=F32, device=dev) for g in gs]
+        db = [torch.empty(b.shape, dtype=F32, device=dev) for b in bs]
+        dxs = [None, None]
+        r0, nr = meta.row0, meta.nrows
+        for v, (hs, ys, st, z, zn, (zmean, zrstd)) in enumerate(views):
+            acc = v > 0
+            dy = batchnorm_bwd(dzn[v], z, zmean, zrstd)
+            gemm_tn(dy, hs[L], dW[L], accumulate=acc)
+            for i in range(L, -1, -1):
+                wt = cached_bf16(Ws[i], transpose_only=True)
+                if i == 0:
+                    if need[v]:
+                        dx = (torch.empty((M, E), dtype=F32, device=dev) if (r0 == 0 and nr == M)
+                              else torch.zeros((M, E), dtype=F32, device=dev))
+                        gemm_nt(dy[r0:r0 + nr], wt, dx[r0:r0 + nr], epi=EPI_F32)
+                        dxs[v] = dx
+                    break
+                dh = gemm_nt(dy, wt, torch.empty((M, Ws[i].shape[1]), dtype=F32, device=dev), epi=EPI_F32)
+                mean, rstd = st[i - 1]
+                dy = batchnorm_bwd(dh, ys[i - 1], mean, rstd, gs[i - 1], bs[i - 1], relu=True, dgamma=dg[i - 1], dbeta=db[i - 1],
+                                   row0=0, nrows=M, accumulate=acc)
+                gemm_tn(dy, hs[i - 1], dW[i - 1], accumulate=acc)
+        ctx.views = ctx.weights = None
+        grads = []
+        for i in range(L):
+            grads += [dW[i], dg[i], db[i]]
+        grads.append(dW[L])
+        grads = [g if need[3 + k] else None for k, g in enumerate(grads)]
+        return (dxs[0], dxs[1], None, *grads)
