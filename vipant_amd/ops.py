@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -97,6 +98,17 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, *, bias=None, aux
     return c
 
 
+def _stats(n: int, device):
+    """(mean, rstd) of a normalisation over n rows (or columns): fp32 [n] each."""
+    return torch.empty((n,), dtype=F32, device=device), torch.empty((n,), dtype=F32, device=device)
+
+
+def mx_buffer(M: int, cols: int, device):
+    """(uint8 [M, cols], uint8 [vipant_mx_scale_bytes(M, cols)]): room for an e4m3 operand and its block scales in the MX layout."""
+    return (torch.empty((M, cols), dtype=torch.uint8, device=device),
+            torch.empty((query("vipant_mx_scale_bytes", M, cols),), dtype=torch.uint8, device=device))
+
+
 def quant_e4m3(x: torch.Tensor, q: torch.Tensor = None, scale: torch.Tensor = None):
     """bf16 rows [M, K] -> (e4m3 bytes [M, K], E8M0 row-scale bytes [M]); see vipant_quant_e4m3_rows."""
     _need(x, BF16, "quant_e4m3.x")
@@ -111,26 +123,22 @@ def quant_e4m3(x: torch.Tensor, q: torch.Tensor = None, scale: torch.Tensor = No
 
 def quant_e4m3_mx(x: torch.Tensor, q: torch.Tensor = None, scale: torch.Tensor = None):
     """bf16 rows [M, K] -> (e4m3 bytes [M, K], E8M0 BLOCK scales, one per 32 elements of a row, in the library's MX layout:
-    vipant_quant_e4m3_mx) -- the form an activation operand of gemm_nt_e4m3 takes."""
+    vipant_quant_e4m3_mx) -- the form an activation operand of gemm_nt_e4m3 takes.  q, scale: both or neither."""
     _need(x, BF16, "quant_e4m3_mx.x")
     M, K = x.shape
-    if q is None:
-        q = torch.empty((M, K), dtype=torch.uint8, device=x.device)
-    if scale is None:
-        scale = torch.empty((query("vipant_mx_scale_bytes", M, K),), dtype=torch.uint8, device=x.device)
+    if q is None and scale is None:
+        q, scale = mx_buffer(M, K, x.device)
     call("vipant_quant_e4m3_mx", x.data_ptr(), x.stride(0), q.data_ptr(), q.stride(0), scale.data_ptr(), M, K, _stream())
     return q, scale
 
 
 def quant_e4m3_mx32(x: torch.Tensor, q: torch.Tensor = None, scale: torch.Tensor = None):
     """bf16 rows [M, K] -> (e4m3 bytes, block scales in the MX layout) with every scale shared by an aligned block of 32 rows x 32
-    columns (vipant_quant_e4m3_mx32): an operand of gemm_tn_e4m3, and as valid an activation operand of gemm_nt_e4m3 as any."""
+    columns (vipant_quant_e4m3_mx32): an operand of gemm_tn_e4m3, a valid activation operand of gemm_nt_e4m3.  q, scale: both or neither."""
     _need(x, BF16, "quant_e4m3_mx32.x")
     M, K = x.shape
-    if q is None:
-        q = torch.empty((M, K), dtype=torch.uint8, device=x.device)
-    if scale is None:
-        scale = torch.empty((query("vipant_mx_scale_bytes", M, K),), dtype=torch.uint8, device=x.device)
+    if q is None and scale is None:
+        q, scale = mx_buffer(M, K, x.device)
     call("vipant_quant_e4m3_mx32", x.data_ptr(), x.stride(0), q.data_ptr(), q.stride(0), scale.data_ptr(), M, K, _stream())
     return q, scale
 
@@ -216,8 +224,7 @@ def layernorm_fwd(x: torch.Tensor, gamma, beta, *, want_bf16=True, want_f32=Fals
     ldx = ldx if ldx is not None else x.stride(0)
     y = torch.empty((M, D), dtype=BF16, device=x.device) if want_bf16 else None
     y32 = torch.empty((M, D), dtype=F32, device=x.device) if want_f32 else None
-    mean = torch.empty((M,), dtype=F32, device=x.device)
-    rstd = torch.empty((M,), dtype=F32, device=x.device)
+    mean, rstd = _stats(M, x.device)
     xsum = torch.empty((M, D), dtype=F16 if sum_f16 else F32, device=x.device) if (add is not None and want_sum) else None
     flags = (_ffi.STREAM_IN_F16 if x.dtype == F16 else 0) | (_ffi.STREAM_OUT_F16 if sum_f16 else 0)
     call("vipant_layernorm_fwd_e4m3", x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), _ptr(y), _ptr(y32),
@@ -380,8 +387,7 @@ def fp8_plan(w=None, w2=None, act=None, dyq=None, emit=None, tn=False, keep=None
 
 def fp8_scratch(M: int, D: int, device):
     """(bytes [M, 4D], block scales) for an e4m3 activation operand of up to 4 D columns."""
-    return (torch.empty((M, 4 * D), dtype=torch.uint8, device=device),
-            torch.empty((query("vipant_mx_scale_bytes", M, 4 * D),), dtype=torch.uint8, device=device))
+    return mx_buffer(M, 4 * D, device)
 
 
 _frozen_cache: Dict[tuple, tuple] = {}
@@ -497,8 +503,7 @@ class PatchEmbedFn(torch.autograd.Function):
         patches = torch.empty((b * P, kcols), dtype=BF16, device=dev)
         tok = torch.empty((b * S, D), dtype=F32, device=dev)
         out = torch.empty((b * S, D), dtype=F32, device=dev)
-        mean = torch.empty((b * S,), dtype=F32, device=dev)
-        rstd = torch.empty((b * S,), dtype=F32, device=dev)
+        mean, rstd = _stats(b * S, dev)
         call("vipant_patch_embed_ln_fwd", x.data_ptr(), conv_w.detach().contiguous().data_ptr(),
              cls.detach().contiguous().data_ptr(), pos.detach().contiguous().data_ptr(), ln_w.detach().data_ptr(),
              ln_b.detach().data_ptr(), w_eff.data_ptr(), patches.data_ptr(), None, tok.data_ptr(), out.data_ptr(),
@@ -555,6 +560,12 @@ class _LayerGrads:
             self.views.append(self.flat[off:off + n].view(s))
             off += p
 
+    def publish(self, grads: list, l: int, params, grad_sync):
+        """Hand block l's gradients to `grads` (12 per block, in parameter order) and start their all-reduce, if any."""
+        grads[12 * l:12 * l + 12] = self.views
+        if grad_sync is not None:
+            grad_sync.reduce_async(self.flat, self.views, params[12 * l:12 * l + 12])
+
 
 # precision of the residual-stream GRADIENT: `running.grad_stream` (bf16 | fp32; monitor.py sets it), default from the environment
 GRAD_STREAM_F32 = os.environ.get("VIPANT_GRAD_STREAM", "bf16") == "fp32"
@@ -610,210 +621,317 @@ def head_extract(full: torch.Tensor, H: int, bias=None) -> torch.Tensor:
     return out
 
 
+class _Stack:
+    """Shapes and switches of one BackboneFn call, read by its forward, its backward (ctx.stack) and every block."""
+
+    def __init__(self, device, batch, S, D, causal, train, fp8, recompute_mlp, stream_f16, ridx, prune):
+        self.dev, self.batch, self.S, self.M, self.D, self.H = device, batch, S, batch * S, D, D // 64
+        self.causal, self.train, self.fp8, self.recompute_mlp = bool(causal), train, bool(fp8), bool(recompute_mlp)
+        self.ridx, self.prune, self.keep_mlp = ridx, prune, train and not recompute_mlp
+        self.keep_q = self.fp8 and train and FP8_TN and D % 128 == 0    # the forward keeps e4m3 forms for the e4m3 weight-gradient contractions
+        self.tn8 = FP8_TN        # (decided by the forward: the backward must read what that forward kept)
+        self.ctx_alg = prune and LAST_BLOCK_CTX and self.H in (8, 12, 16) and S <= 1024
+        # `running.stream_dtype: fp16`: inside the stack the residual stream is kept in the reference's own autocast precision
+        # (clip/model.py:157-160) -- every LayerNorm pass reads and writes 2 instead of 4 bytes per element of it, and so do the
+        # saved copies the backward reads; statistics stay fp32, the norm is taken on the unrounded sum, and the tensors that
+        # cross the autograd boundary (the stack's input and output) stay fp32
+        self.sdt = F16 if stream_f16 else F32
+
+    def sflags(self, t):
+        return (_ffi.STREAM_IN_F16 if t.dtype == F16 else 0) | (_ffi.STREAM_OUT_F16 if self.sdt == F16 else 0)
+
+    def new(self, cols, dtype=BF16, rows=None):
+        return torch.empty((self.M if rows is None else rows, cols), dtype=dtype, device=self.dev)
+
+
+class _Record:
+    """A block's state between its forward and its backward, by name; a field the forward did not set is None."""
+    __slots__ = ()
+
+    def __init__(self, **fields):
+        for k in self.__slots__:
+            setattr(self, k, fields.pop(k, None))
+        assert not fields, fields
+
+
+class _Block(_Record):
+    """What a full block's backward reads: activations (an e4m3 form as ONE (bytes, block scales) pair: h1q, h2q, oq, gq), W^T of
+    in_proj, out_proj, c_fc, c_proj (bf16 wt, e4m3 wtq) and c_fc's W (bf16 wfc_b, e4m3 q_fc) for the MLP recomputation."""
+    __slots__ = ("x", "mean1", "rstd1", "h1", "h1q", "qkv", "o", "oq", "lse", "x1", "mean2", "rstd2", "h2", "h2q", "u", "g", "gq",
+                 "wt", "wtq", "wfc_b", "q_fc")
+
+
+class _RowsBlock(_Record):
+    """What the backward of the last block on the read-out rows reads (*_r: `batch` rows; wqkv_b: in_proj W of the folded form)."""
+    __slots__ = ("x", "mean1", "rstd1", "h1", "qkv", "q_r", "probs", "o_r", "h1_r", "x1_r", "mean2_r", "rstd2_r", "h2_r", "u_r", "g_r",
+                 "wt", "wqkv_b")
+
+
+def _block_fwd(s: _Stack, b: _Block, x, y_prev, p, wb, wq, tmp):
+    """One full block forward; `b` receives the activations (buffers of its own when training, the shared temporaries `tmp` of a
+    frozen tower).  Returns (x1, y2): the stream after the attention half and the MLP branch's output, added by the next LayerNorm."""
+    M, D, H, new, fp8, st = s.M, s.D, s.H, s.new, s.fp8, _stream()
+    ln1w, ln1b, _, bqkv, _, bo, ln2w, ln2b, _, bfc, _, bpr = p
+    (wqkv_b, wo_b, wfc_b, wpr_b), (q_qkv, q_o, q_fc, q_pr) = wb, wq or (None,) * 4
+    emit_o = fp8 and H % 2 == 0 and ATTN_EMIT     # the attention kernel leaves its output's e4m3 form, what out_proj reads
+    if not s.train:
+        b.h1, b.h2, b.qkv, y1, y2 = tmp.h1, tmp.h2, tmp.qkv, tmp.y1, tmp.y2
+        b.mean1, b.rstd1 = b.mean2, b.rstd2 = tmp.stats
+    else:
+        b.qkv, y1, y2 = new(3 * D), new(D), new(D)
+        (b.mean1, b.rstd1), (b.mean2, b.rstd2) = _stats(M, s.dev), _stats(M, s.dev)
+        if s.keep_q:
+            # e4m3 weight gradients: of the two LayerNorm outputs and of g the backward reads the e4m3 forms alone (block-uniform
+            # scales: static ones from the LayerNorm passes, the c_fc epilogue's for g) -- 1 instead of 2 bytes per element kept, and
+            # the bf16 tensors are never written; the attention output's e4m3 form (what out_proj reads) is kept beside the bf16 one
+            # the attention backward needs
+            b.oq = mx_buffer(M, D, s.dev) if emit_o else None
+            b.h1q, b.h2q = mx_buffer(M, D, s.dev), mx_buffer(M, D, s.dev)
+        else:
+            b.h1, b.h2 = new(D), new(D)
+            # `recompute_mlp` under e4m3: the LayerNorm output's e4m3 form is kept beside it (M D bytes + scales per block), so
+            # that the backward's c_fc launch needs no quantisation pass either
+            b.h2q = mx_buffer(M, D, s.dev) if (fp8 and s.recompute_mlp) else None
+        if s.keep_mlp:      # u: 8-bit codes of QuickGELU'(pre-activation) -- all the backward needs of it
+            b.u = new(4 * D, torch.uint8)
+            b.gq, b.g = (mx_buffer(M, 4 * D, s.dev), None) if s.keep_q else (None, new(4 * D))
+    u, g = (b.u, b.g) if s.keep_mlp else (tmp.u, tmp.g)
+    # ln_1 (+ residual add of the previous block's MLP branch: x <- x + y2_prev) + in_proj
+    xs = new(D, s.sdt) if y_prev is not None else None
+    call("vipant_ln_qkv_fwd_e4m3", x.data_ptr(), _ptr(y_prev), _ptr(xs), ln1w.data_ptr(), ln1b.data_ptr(), wqkv_b.data_ptr(),
+         bqkv.data_ptr(), _ptr(b.h1), b.mean1.data_ptr(), b.rstd1.data_ptr(), b.qkv.data_ptr(), M, D,
+         C.byref(fp8_plan(q_qkv, None, b.h1q or tmp.act)) if fp8 else None, s.sflags(x), st)
+    b.x = x = xs if xs is not None else x
+    q8 = (b.oq or tmp.act) if emit_o else None
+    b.o, b.lse = mha_fwd(b.qkv, s.batch, s.S, H, s.causal, q8=q8)
+    call("vipant_gemm_bias_residual_fwd_e4m3", None if q8 else b.o.data_ptr(), wo_b.data_ptr(), bo.data_ptr(), None, y1.data_ptr(),
+         M, D, D, C.byref(fp8_plan(q_o, None, q8 or tmp.act)) if fp8 else None, st)
+    # ln_2 (+ residual add of the attention branch) + c_fc + QuickGELU + c_proj
+    b.x1 = new(D, s.sdt)
+    if "gemm_nt" in KERNEL_PROBE and not fp8:     # bench.py times the c_fc launch alone: the same three launches, issued one by one
+        call("vipant_layernorm_fwd_e4m3", x.data_ptr(), D, ln2w.data_ptr(), ln2b.data_ptr(), b.h2.data_ptr(), None,
+             b.mean2.data_ptr(), b.rstd2.data_ptr(), M, D, y1.data_ptr(), b.x1.data_ptr(), None, None, s.sflags(x), st)
+        gemm_nt(b.h2, wfc_b, g, bias=bfc, aux=u, epi=EPI_QUICKGELU_D8)
+        gemm_nt(g, wpr_b, y2, bias=bpr, epi=EPI_BF16)
+    else:
+        only_q = fp8 and not s.keep_mlp        # c_proj's operand is all that is wanted of g: neither g nor the codes are written
+        call("vipant_ln_mlp_quickgelu_fwd_e4m3", x.data_ptr(), y1.data_ptr(), b.x1.data_ptr(), ln2w.data_ptr(), ln2b.data_ptr(),
+             wfc_b.data_ptr(), bfc.data_ptr(), wpr_b.data_ptr(), bpr.data_ptr(), _ptr(b.h2), b.mean2.data_ptr(),
+             b.rstd2.data_ptr(), None if only_q else u.data_ptr(), None if (only_q or g is None) else g.data_ptr(), y2.data_ptr(), M, D,
+             C.byref(fp8_plan(q_fc, q_pr, b.h2q or tmp.act, emit=b.gq or tmp.emit)) if fp8 else None, s.sflags(x), st)
+    return b.x1, y2
+
+
+def _rows_block_fwd(s: _Stack, b: _RowsBlock, x, y_prev, p, wb, tmp):
+    """The last block on the read-out rows: bf16 contractions whatever `fp8` says -- all of them launches on `batch` or `batch * H`
+    rows.  (Only the round-3 form, VIPANT_LAST_BLOCK_CTX=0, still has a per-token launch here, the K / V projection, N = 2 D: it
+    stays bf16 too, a documented departure from `running.fp8_gemm` for 1 of 97 contraction launches.)  `running.last_block_rows=False`
+    restores the e4m3 last block; both corners are under test_end_to_end_golden_e4m3.  Returns the rows' output, fp32 [batch, D]."""
+    M, D, H, batch, S, ridx, new, dev, st = s.M, s.D, s.H, s.batch, s.S, s.ridx, s.new, s.dev, _stream()
+    ln1w, ln1b, wqkv, bqkv, _, bo, ln2w, ln2b, _, bfc, _, bpr = p
+    wqkv_b, wo_b, wfc_b, wpr_b = wb
+    # (training: the last block keeps its per-token activations for the read-out rows only)
+    b.h1, (b.mean1, b.rstd1) = (new(D), _stats(M, dev)) if s.train else (tmp.h1, tmp.stats)
+    xs = new(D, s.sdt) if y_prev is not None else None
+    call("vipant_layernorm_fwd_e4m3", x.data_ptr(), D, ln1w.data_ptr(), ln1b.data_ptr(), b.h1.data_ptr(), None,
+         b.mean1.data_ptr(), b.rstd1.data_ptr(), M, D, _ptr(y_prev), _ptr(xs), None, None, s.sflags(x), st)
+    b.x = x = xs if xs is not None else x
+    b.h1_r = gather_rows(b.h1, ridx, batch, S)
+    b.q_r = gemm_nt(b.h1_r, wqkv_b[:D], new(D, rows=batch), bias=bqkv[:D], epi=EPI_BF16, few_rows=True)     # Q of the read-out rows
+    b.probs = torch.empty((batch, H, S), dtype=F32, device=dev)
+    if s.ctx_alg:
+        # one query per (item, head): the key projection moves to the query (qk_h = W_k,h^T q_h, the key bias drops out of the
+        # softmax), the value projection behind the weighted sum (o_h = W_v,h sum_j p_j h1_j + b_v,h): two per-head contractions on
+        # `batch` rows and one pass over h1 instead of K, V of every token
+        wk_t = (b.wt[0] if s.train else cached_bf16(wqkv, transpose_only=True))[:, D:2 * D]
+        # qk and the heads' contexts travel as bf16 PAIRS (hi + lo planes, round 5): [0]: qk, [1]: contexts
+        b.qkv = torch.empty((2, 2, batch * H, D), dtype=BF16, device=dev)
+        heads_to_wide(b.q_r, wk_t, b.qkv[0], H)
+        call("vipant_rows_ctx_fwd", b.qkv[0].data_ptr(), b.h1.data_ptr(), _ptr(ridx), b.qkv[1].data_ptr(), b.probs.data_ptr(),
+             batch, S, H, int(s.causal), 1, st)
+        b.o_r = wide_to_heads(b.qkv[1], wqkv_b[2 * D:], H, bias=bqkv[2 * D:])
+    else:
+        b.qkv = new(3 * D) if s.train else tmp.qkv
+        gemm_nt(b.h1, wqkv_b[D:], b.qkv[:, D:], bias=bqkv[D:], epi=EPI_BF16)         # K, V of every token
+        b.o_r = new(D, rows=batch)
+        call("vipant_mha_rows_fwd", b.q_r.data_ptr(), b.qkv.data_ptr(), _ptr(ridx), b.o_r.data_ptr(), b.probs.data_ptr(), batch, S,
+             H, int(s.causal), st)
+    y1_r = gemm_nt(b.o_r, wo_b, new(D, rows=batch), bias=bo, epi=EPI_BF16, few_rows=True)
+    x_r = gather_rows(x, ridx, batch, S)
+    # the read-out rows' stream stays fp32 from here, and c_proj adds it in its epilogue: the rows the features are read from skip
+    # the two roundings (fp16 stream, bf16 branch output) the full block would give them
+    b.x1_r, b.h2_r, b.u_r, b.g_r = new(D, F32, batch), new(D, rows=batch), new(4 * D, torch.uint8, batch), new(4 * D, rows=batch)
+    b.mean2_r, b.rstd2_r = _stats(batch, dev)
+    call("vipant_layernorm_fwd_e4m3", x_r.data_ptr(), D, ln2w.data_ptr(), ln2b.data_ptr(), b.h2_r.data_ptr(), None,
+         b.mean2_r.data_ptr(), b.rstd2_r.data_ptr(), batch, D, y1_r.data_ptr(), b.x1_r.data_ptr(), None, None,
+         _ffi.STREAM_IN_F16 if x_r.dtype == F16 else 0, st)
+    gemm_nt(b.h2_r, wfc_b, b.g_r, bias=bfc, aux=b.u_r, epi=EPI_QUICKGELU_D8, few_rows=True)
+    return gemm_nt(b.g_r, wpr_b, new(D, F32, batch), bias=bpr, aux=b.x1_r, epi=EPI_RESIDUAL_F32, few_rows=True)
+
+
+def _block_bwd(s: _Stack, b: _Block, p, lg: _LayerGrads, lg_below: Optional[_LayerGrads], dx, dx_b, dyq, tmp):
+    """One full block backward, in place on the stream gradient: dx (fp32 master | None), dx_b (bf16), dyq (its e4m3 form | None).
+    The block's parameter gradients go to `lg`, d c_proj.bias of the block below to `lg_below`."""
+    M, D, H, fp8, kq, ws, st = s.M, s.D, s.H, s.fp8, s.keep_q, tmp.ws, _stream()
+    ln1w, _, _, _, _, _, ln2w, _, _, bfc, _, _ = p
+    (wqkv_t, wo_t, wfc_t, wpr_t), (tq_qkv, tq_o, tq_fc, tq_pr) = b.wt, b.wtq or (None,) * 4
+    d_ln1w, d_ln1b, d_wqkv, d_bqkv, d_wo, d_bo, d_ln2w, d_ln2b, d_wfc, d_bfc, d_wpr, d_bpr = lg.views
+    if s.recompute_mlp:
+        # (e4m3 weight gradients: the recomputation leaves g's e4m3 form -- the same epilogue, the same bytes as a forward that keeps
+        # it -- and no bf16 g)
+        u, g, keep = tmp.u, tmp.g, tmp.gq
+        call("vipant_mlp_quickgelu_recompute_e4m3", None if fp8 else b.h2.data_ptr(), b.wfc_b.data_ptr(), bfc.data_ptr(), u.data_ptr(),
+             None if kq else g.data_ptr(), M, D, C.byref(fp8_plan(b.q_fc, None, b.h2q, emit=keep)) if fp8 else None, st)
+        if not kq:
+            b.h2q = None        # read by the recomputation alone
+    else:
+        u, g, keep = b.u, b.g, b.gq
+    keep1, keep2 = (b.h1q, b.h2q) if kq else (None, None)     # h1, h2 (and g) as the e4m3 forms the forward kept
+    # MLP half: c_proj^T + QuickGELU', c_fc^T, both weight gradients, ln_2 backward (+ residual gradient);
+    # the produced stream gradient is also d(out_proj output): its column sum is d out_proj.bias
+    call("vipant_ln_mlp_quickgelu_bwd_e4m3", dx_b.data_ptr(), wpr_t.data_ptr(), wfc_t.data_ptr(), u.data_ptr(),
+         None if keep else g.data_ptr(), None if keep2 else b.h2.data_ptr(), b.x1.data_ptr(), b.mean2.data_ptr(), b.rstd2.data_ptr(),
+         ln2w.data_ptr(), _ptr(dx), dx_b.data_ptr(), _ptr(tmp.du), tmp.dh.data_ptr(), d_wpr.data_ptr(), d_wfc.data_ptr(),
+         d_bfc.data_ptr(), d_ln2w.data_ptr(), d_ln2b.data_ptr(), d_bo.data_ptr(), M, D, ws.data_ptr(), ws.numel(),
+         C.byref(fp8_plan(tq_pr, tq_fc, tmp.act, dyq, emit=tmp.emit, tn=s.tn8, keep=keep, keep2=keep2)) if fp8 else None,
+         _ffi.STREAM_IN_F16 if b.x1.dtype == F16 else 0, st)
+    # attention half: out_proj^T, attention core, in_proj^T + ln_1 backward; the produced stream gradient is
+    # d(c_proj output) of the block below: its column sum is that block's d c_proj.bias
+    call("vipant_gemm_bias_residual_bwd_e4m3", dx_b.data_ptr(), wo_t.data_ptr(), b.o.data_ptr(), tmp.do.data_ptr(), d_wo.data_ptr(),
+         M, D, D, ws.data_ptr(), ws.numel(),
+         C.byref(fp8_plan(tq_o, None, tmp.act, dyq, emit=tmp.emit, tn=s.tn8, keep=b.oq)) if fp8 else None, st)
+    q8 = tmp.act if (fp8 and H % 2 == 0 and ATTN_EMIT) else None
+    dqkv = mha_bwd(b.qkv, b.o, tmp.do, b.lse, s.batch, s.S, H, s.causal, q8=q8)
+    call("vipant_ln_qkv_bwd_e4m3", dqkv.data_ptr(), wqkv_t.data_ptr(), None if keep1 else b.h1.data_ptr(), b.x.data_ptr(),
+         b.mean1.data_ptr(), b.rstd1.data_ptr(), ln1w.data_ptr(), _ptr(dx), dx_b.data_ptr(), tmp.dh.data_ptr(), d_wqkv.data_ptr(),
+         d_bqkv.data_ptr(), d_ln1w.data_ptr(), d_ln1b.data_ptr(), lg_below.views[11].data_ptr() if lg_below is not None else None,
+         M, D, ws.data_ptr(), ws.numel(), C.byref(fp8_plan(tq_qkv, None, tmp.act, dyq, emit=tmp.emit, tn=s.tn8, keep=keep1)) if fp8 else None,
+         (_ffi.STREAM_IN_F16 if b.x.dtype == F16 else 0) | (_ffi.STREAM_ACT_Q if q8 else 0), st)
+
+
+def _rows_block_bwd(s: _Stack, b: _RowsBlock, p, lg: _LayerGrads, lg_below: Optional[_LayerGrads], dxr_b, tmp):
+    """The last block on the read-out rows, backward from dxr_b (bf16 [batch, D]): the two block operators of the MLP / out_proj half
+    on `batch` rows, the one-query attention backward, then the K / V half of in_proj and ln_1 on every token.  Returns the stream
+    gradient below it, (dx, dx_b, dyq)."""
+    M, D, H, batch, S, ridx, dev, ws, dh, st = s.M, s.D, s.H, s.batch, s.S, s.ridx, s.dev, tmp.ws, tmp.dh, _stream()
+    ln1w, _, _, _, _, _, ln2w, _, _, _, _, _ = p
+    wqkv_t, wo_t, wfc_t, wpr_t = b.wt
+    d_ln1w, d_ln1b, d_wqkv, d_bqkv, d_wo, d_bo, d_ln2w, d_ln2b, d_wfc, d_bfc, d_wpr, d_bpr = lg.views
+    du_r, dh_r, do_r = s.new(4 * D, rows=batch), s.new(D, rows=batch), s.new(D, rows=batch)
+    call("vipant_ln_mlp_quickgelu_bwd_e4m3", dxr_b.data_ptr(), wpr_t.data_ptr(), wfc_t.data_ptr(), b.u_r.data_ptr(),
+         b.g_r.data_ptr(), b.h2_r.data_ptr(), b.x1_r.data_ptr(), b.mean2_r.data_ptr(), b.rstd2_r.data_ptr(), ln2w.data_ptr(), None,
+         dxr_b.data_ptr(), du_r.data_ptr(), dh_r.data_ptr(), d_wpr.data_ptr(), d_wfc.data_ptr(), d_bfc.data_ptr(),
+         d_ln2w.data_ptr(), d_ln2b.data_ptr(), d_bo.data_ptr(), batch, D, ws.data_ptr(), ws.numel(), None,
+         (_ffi.STREAM_IN_F16 if b.x1_r.dtype == F16 else 0) | _ffi.STREAM_FEW_ROWS, st)
+    # out_proj backward on the rows (vipant_gemm_bias_residual_bwd's two launches, the first as a few-rows launch)
+    gemm_nt(dxr_b, wo_t, do_r, epi=EPI_BF16, few_rows=True)
+    gemm_tn(dxr_b, b.o_r, d_wo, ws_name="block_bwd")
+    if s.ctx_alg:
+        # qkv = [qk | contexts] of the forward.  dctx_h = W_v,h^T do_h; the kernel gives dh of every token and dqk;
+        # dq_h = W_k,h dqk_h; d W_v = do (x) ctx, d W_k = q (x) dqk per head (block-sparse operands), d b_k = 0
+        # (qk, the contexts and dqk are bf16 pairs; the two weight gradients take the hi planes: their own rounding, fp32
+        # sums over `batch * H` bf16 products, is the larger term)
+        qk, hctx = b.qkv[0], b.qkv[1]
+        dctx = heads_to_wide(do_r, wqkv_t[:, 2 * D:], torch.empty((batch * H, D), dtype=BF16, device=dev), H)
+        gemm_tn(head_expand(do_r, H), hctx[0], d_wqkv[2 * D:], a_colsum=d_bqkv[2 * D:], ws_name="block_bwd")
+        dqk = torch.empty((2, batch * H, D), dtype=BF16, device=dev)
+        call("vipant_rows_ctx_bwd", qk.data_ptr(), dctx.data_ptr(), hctx.data_ptr(), b.h1.data_ptr(), _ptr(ridx),
+             b.probs.data_ptr(), dh.data_ptr(), dqk.data_ptr(), d_bqkv[D:2 * D].data_ptr(), batch, S, H, int(s.causal), 1, st)
+        dq_r = wide_to_heads(dqk, b.wqkv_b[D:2 * D], H)
+        gemm_tn(head_expand(b.q_r, H), dqk[0], d_wqkv[D:2 * D], ws_name="block_bwd")
+        del dctx, dqk
+    else:
+        dq_r, dqkv = s.new(D, rows=batch), s.new(3 * D)
+        call("vipant_mha_rows_bwd", b.q_r.data_ptr(), b.qkv.data_ptr(), _ptr(ridx), b.probs.data_ptr(), do_r.data_ptr(),
+             dq_r.data_ptr(), dqkv.data_ptr(), batch, S, H, int(s.causal), st)
+        # dh = dK|dV . W_kv on every token
+        gemm_nt(dqkv[:, D:], wqkv_t[:, D:], dh, epi=EPI_BF16)
+        gemm_tn(dqkv[:, D:], b.h1, d_wqkv[D:], a_colsum=d_bqkv[D:], ws_name="block_bwd")
+        del dqkv
+    # + dq . W_q on the read-out rows
+    dhq = gemm_nt(dq_r, wqkv_t[:, :D], torch.empty((batch, D), dtype=F32, device=dev), epi=EPI_F32, few_rows=True)
+    call("vipant_add_rows_bf16", dh.data_ptr(), _ptr(ridx), dhq.data_ptr(), 1, batch, S, D, st)
+    gemm_tn(dq_r, b.h1_r, d_wqkv[:D], a_colsum=d_bqkv[:D], ws_name="block_bwd")
+    # ln_1 backward on every token; the residual gradient of this block exists on the read-out rows only
+    dx_b = torch.empty((M, D), dtype=BF16, device=dev)
+    call("vipant_layernorm_bwd_e4m3", dh.data_ptr(), _ffi.LN_X_F16 if b.x.dtype == F16 else 0, b.x.data_ptr(), D,
+         b.mean1.data_ptr(), b.rstd1.data_ptr(), ln1w.data_ptr(), None, None, D, dx_b.data_ptr(), d_ln1w.data_ptr(),
+         d_ln1b.data_ptr(), lg_below.views[11].data_ptr() if lg_below is not None else None, 0, M, D, ws.data_ptr(),
+         ws.numel(), None, None, st)
+    call("vipant_add_rows_bf16", dx_b.data_ptr(), _ptr(ridx), dxr_b.data_ptr(), 0, batch, S, D, st)
+    if lg_below is not None:
+        colsum(dxr_b, lg_below.views[11], accumulate=True)
+    dx = s.new(D, F32) if GRAD_STREAM_F32 else None
+    if dx is not None:
+        call("vipant_cast_f32", dx_b.data_ptr(), dx.data_ptr(), M * D, st)
+    return dx, dx_b, (quant_e4m3_mx(dx_b) if s.fp8 else None)
+
+
 class BackboneFn(torch.autograd.Function):
     """TransformerBackbone.forward = L x ResidualAttentionBlock (cvap/module/val.py:493-522) on the fp32
     residual stream x [batch*S, D].  One autograd node for the whole stack: the layer loop, the saved
     activations and the (fp32, bf16) gradient-stream pair between layers are managed here, not by autograd.
     Per block four entry points of the fused operator set each way (include/vipant_hip.h): vipant_ln_qkv_*, vipant_mha_*,
-    vipant_gemm_bias_residual_*, vipant_ln_mlp_quickgelu_*.
+    vipant_gemm_bias_residual_*, vipant_ln_mlp_quickgelu_*.  Each block runs through _block_fwd / _block_bwd; what its backward
+    reads of its forward is one named record per block (_Block), kept on ctx and dropped as soon as that block's backward is done.
 
     `rows` (None | "first" | int64 [batch]): the caller will read ONE row per item of the output -- the class token
     (ViTPostEncoder, cvap/module/val.py:288-289) or the end-of-text token (GPTPostEncoder, val.py:143-145) -- and the node returns
-    just those rows, [batch, D].  The last block is then evaluated on them alone (csrc/readout_rows.hip): ln_1 and the key / value
-    projection see every token, the query projection, the attention (one query per item and head), out_proj, ln_2 and the MLP see
-    `batch` rows, forward and backward.  Exact: the other rows of the last block's output are never read and carry no gradient, so
-    every feature and every parameter gradient is what the full block gives (tests/test_model_gpu.py, against the reference's
-    vectors and against rows=None)."""
+    just those rows, [batch, D].  The last block is then evaluated on them alone (_rows_block_fwd / _rows_block_bwd, record
+    _RowsBlock; csrc/readout_rows.hip): ln_1 and the key / value projection see every token, the query projection, the attention
+    (one query per item and head), out_proj, ln_2 and the MLP see `batch` rows, forward and backward.  Exact: the other rows of the
+    last block's output are never read and carry no gradient, so every feature and every parameter gradient is what the full block
+    gives (tests/test_model_gpu.py, against the reference's vectors and against rows=None)."""
 
     @staticmethod
-    def forward(ctx, x, batch, S, causal, grad_sync, recompute_mlp, fp8, stream_f16, rows, *params):
-        _need(x, F32, "backbone.x")
-        x_in = x
-        M, D = x.shape
+    def forward(ctx, x_in, batch, S, causal, grad_sync, recompute_mlp, fp8, stream_f16, rows, *params):
+        _need(x_in, F32, "backbone.x")
+        (M, D), L = x_in.shape, len(params) // 12
         assert M == batch * S and len(params) % 12 == 0
-        L, H = len(params) // 12, D // 64
-        prune = rows is not None and L > 0
         ridx = rows if isinstance(rows, torch.Tensor) else None
         if ridx is not None:
             _need(ridx, I64, "backbone.rows")
             assert ridx.numel() == batch and ridx.is_contiguous()
-        train = any(ctx.needs_input_grad)
-        dev = x.device
-        st = _stream()
-        saved: List[torch.Tensor] = []
-        wts: List[Tuple[torch.Tensor, ...]] = []
-        kept_q: List = []           # per full block: (bytes, block scales) of ln_2's output (e4m3 towers with recompute_mlp)
-        x = x.contiguous()
-
-        def new(cols, dtype=BF16):
-            return torch.empty((M, cols), dtype=dtype, device=dev)
-        # `running.stream_dtype: fp16`: inside the stack the residual stream is kept in the reference's own autocast precision
-        # (clip/model.py:157-160) -- every LayerNorm pass reads and writes 2 instead of 4 bytes per element of it, and so do the
-        # saved copies the backward reads; statistics stay fp32, the norm is taken on the unrounded sum, and the tensors that
-        # cross the autograd boundary (the stack's input and output) stay fp32
-        SDT = F16 if stream_f16 else F32
-        out16 = _ffi.STREAM_OUT_F16 if stream_f16 else 0
-
-        def sflags(t):
-            return (_ffi.STREAM_IN_F16 if t.dtype == F16 else 0) | out16
+        x = x0 = x_in.contiguous()
+        s = _Stack(x.device, batch, S, D, causal, any(ctx.needs_input_grad), fp8, recompute_mlp, stream_f16, ridx,
+                   rows is not None and L > 0)
         # Per block (cvap/module/val.py:519-522):  x1 = x + attn(ln_1(x));  x2 = x1 + mlp(ln_2(x1)).
         # The branch outputs y1, y2 leave their contraction as bf16 and the residual add is fused into the NEXT
         # LayerNorm pass (fp32 stream in, fp32 stream + bf16 normalised activations out), so every contraction has a
         # plain single-output bf16 epilogue and the fp32 stream is only touched by the streaming LN kernels.
-        keep_mlp = train and not recompute_mlp
-        if not train:   # frozen tower: one set of temporaries for all layers
-            h1, h2, qkv, y1, y2 = new(D), new(D), new(3 * D), new(D), new(D)
-            mean = torch.empty((M,), dtype=F32, device=dev); rstd = torch.empty((M,), dtype=F32, device=dev)
-        fp8 = bool(fp8)
-        keep_q = fp8 and train and FP8_TN and D % 128 == 0      # the forward keeps e4m3 forms for the e4m3 weight-gradient contractions
-        kept_s: List = []           # per full block: the block scales of the kept e4m3 forms
+        tmp = SimpleNamespace(u=None, g=None, act=None, emit=None)      # temporaries every block shares
+        if not s.train:     # frozen tower: one set of temporaries for all layers
+            tmp.h1, tmp.h2, tmp.qkv, tmp.y1, tmp.y2, tmp.stats = s.new(D), s.new(D), s.new(3 * D), s.new(D), s.new(D), _stats(M, s.dev)
         # (e4m3 towers that do not keep the MLP activations need neither: the c_fc epilogue leaves g's e4m3 form for c_proj and nothing else)
-        if not keep_mlp and not fp8:        # u: 8-bit codes of QuickGELU'(pre-activation) -- all the backward needs of it
-            u, g = new(4 * D, torch.uint8), new(4 * D)
-        y_prev = None
-        ctx_alg = prune and LAST_BLOCK_CTX and H in (8, 12, 16) and S <= 1024
+        if not s.keep_mlp and not s.fp8:
+            tmp.u, tmp.g = s.new(4 * D, torch.uint8), s.new(4 * D)
         # e4m3 operands in the NT contractions (configs[4]): a property of the tower, whether or not this call records a backward --
         # the no-grad feature pass of `running.micro_batch` and evaluation must see the forward the training pass differentiates
-        if train or fp8:        # bf16 copies (W and W^T) of the 4 L weight matrices: one launch per step
+        if s.train or s.fp8:        # bf16 copies (W and W^T) of the 4 L weight matrices: one launch per step
             mats = [params[12 * l + i] for l in range(L) for i in (2, 4, 8, 10)]
-            if fp8:
-                wb_all, wt_all, wq_all, wtq_all = cast_weights(mats, e4m3=True)
-                act, emit = fp8_scratch(M, D, dev), fp8_scratch(M, D, dev)
-            else:
-                wb_all, wt_all = cast_weights(mats)
+            wb_all, wt_all, wq_all, wtq_all = cast_weights(mats, e4m3=True) if s.fp8 else (*cast_weights(mats), None, None)
+            if s.fp8:
+                tmp.act, tmp.emit = fp8_scratch(M, D, s.dev), fp8_scratch(M, D, s.dev)
+        blocks, y_prev = [], None
         for l in range(L):
-            ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr = (p.detach() for p in params[12 * l:12 * l + 12])
-            if fp8:
-                q_qkv, q_o, q_fc, q_pr = wq_all[4 * l:4 * l + 4]
-            if train:
-                wqkv_b, wo_b, wfc_b, wpr_b = wb_all[4 * l:4 * l + 4]
-                wqkv_t, wo_t, wfc_t, wpr_t = wt_all[4 * l:4 * l + 4]
-                wts.append((wqkv_t, wo_t, wfc_t, wpr_t, wfc_b if recompute_mlp else None) +
-                           ((wq_all[4 * l:4 * l + 4], wtq_all[4 * l:4 * l + 4]) if fp8 else (None, None)))
-                if prune and l == L - 1:         # the last block keeps its per-token activations for the read-out rows only
-                    h1, qkv = new(D), (None if ctx_alg else new(3 * D))
-                    mean1, rstd1 = (torch.empty((M,), dtype=F32, device=dev) for _ in range(2))
-                else:
-                    qkv, y1, y2 = new(3 * D), new(D), new(D)
-                    mean1, rstd1, mean2, rstd2 = (torch.empty((M,), dtype=F32, device=dev) for _ in range(4))
-                    if keep_q:
-                        # e4m3 weight gradients: of the two LayerNorm outputs and of g the backward reads the e4m3 forms alone (block-
-                        # uniform scales: static ones from the LayerNorm passes, the c_fc epilogue's for g) -- 1 instead of 2 bytes per
-                        # element kept, and the bf16 tensors are never written; the attention output's e4m3 form (what out_proj reads)
-                        # is kept beside the bf16 one the attention backward needs
-                        h1 = h2 = None
-                        oq = (new(D, torch.uint8), torch.empty((query("vipant_mx_scale_bytes", M, D),), dtype=torch.uint8, device=dev)) if (H % 2 == 0 and ATTN_EMIT) else None
-                        h1q, h2q = (new(D, torch.uint8), torch.empty((query("vipant_mx_scale_bytes", M, D),), dtype=torch.uint8, device=dev)), (new(D, torch.uint8), torch.empty((query("vipant_mx_scale_bytes", M, D),), dtype=torch.uint8, device=dev))
-                    else:
-                        h1, h2 = new(D), new(D)
-                    if keep_mlp and keep_q:
-                        u, g = new(4 * D, torch.uint8), None
-                        gq = (new(4 * D, torch.uint8), torch.empty((query("vipant_mx_scale_bytes", M, 4 * D),), dtype=torch.uint8, device=dev))
-                    elif keep_mlp:
-                        u, g = new(4 * D, torch.uint8), new(4 * D)
+            p = [t.detach() for t in params[12 * l:12 * l + 12]]
+            mine = slice(4 * l, 4 * l + 4)          # this block's in_proj, out_proj, c_fc, c_proj in the weight lists
+            wb = wb_all[mine] if (s.train or s.fp8) else [cached_bf16(p[i]) for i in (2, 4, 8, 10)]
+            wq = wq_all[mine] if s.fp8 else None
+            wt, wtq = (wt_all[mine], wtq_all[mine] if s.fp8 else None) if s.train else (None, None)
+            if s.prune and l == L - 1:
+                b = _RowsBlock(wt=wt, wqkv_b=wb[0] if s.ctx_alg else None)
+                x, y_prev = _rows_block_fwd(s, b, x, y_prev, p, wb, tmp), None
             else:
-                wqkv_b, wo_b, wfc_b, wpr_b = wb_all[4 * l:4 * l + 4] if fp8 else (cached_bf16(w) for w in (wqkv, wo, wfc, wpr))
-                mean1 = mean2 = mean; rstd1 = rstd2 = rstd
-            if prune and l == L - 1:
-                # the last block on the read-out rows: bf16 contractions whatever `fp8` says -- all of them launches on `batch` or
-                # `batch * H` rows.  (Only the round-3 form, VIPANT_LAST_BLOCK_CTX=0, still has a per-token launch here, the K / V
-                # projection, N = 2 D: it stays bf16 too, a documented departure from `running.fp8_gemm` for 1 of 97 contraction
-                # launches.)  `running.last_block_rows=False` restores the e4m3 last block; both corners are under
-                # test_end_to_end_golden_e4m3
-                def newr(cols, dtype=BF16):
-                    return torch.empty((batch, cols), dtype=dtype, device=dev)
-                xs = new(D, SDT) if y_prev is not None else None
-                call("vipant_layernorm_fwd_e4m3", x.data_ptr(), D, ln1w.data_ptr(), ln1b.data_ptr(), h1.data_ptr(), None,
-                     mean1.data_ptr(), rstd1.data_ptr(), M, D, _ptr(y_prev), _ptr(xs), None, None, sflags(x), st)
-                if xs is not None:
-                    x = xs
-                h1_r = gather_rows(h1, ridx, batch, S)
-                q_r = gemm_nt(h1_r, wqkv_b[:D], newr(D), bias=bqkv[:D], epi=EPI_BF16, few_rows=True)     # Q of the read-out rows
-                probs = torch.empty((batch, H, S), dtype=F32, device=dev)
-                if ctx_alg:
-                    # one query per (item, head): the key projection moves to the query (qk_h = W_k,h^T q_h, the key bias drops out
-                    # of the softmax), the value projection behind the weighted sum (o_h = W_v,h sum_j p_j h1_j + b_v,h): two
-                    # per-head contractions on `batch` rows and one pass over h1 instead of K, V of every token
-                    wk_t = (wqkv_t if train else cached_bf16(wqkv, transpose_only=True))[:, D:2 * D]
-                    # qk and the heads' contexts travel as bf16 PAIRS (hi + lo planes, round 5): [0]: qk, [1]: contexts
-                    qkv = torch.empty((2, 2, batch * H, D), dtype=BF16, device=dev)
-                    heads_to_wide(q_r, wk_t, qkv[0], H)
-                    call("vipant_rows_ctx_fwd", qkv[0].data_ptr(), h1.data_ptr(), _ptr(ridx), qkv[1].data_ptr(), probs.data_ptr(),
-                         batch, S, H, int(causal), 1, st)
-                    o_r = wide_to_heads(qkv[1], wqkv_b[2 * D:], H, bias=bqkv[2 * D:])
-                else:
-                    if qkv is None:
-                        qkv = new(3 * D)
-                    gemm_nt(h1, wqkv_b[D:], qkv[:, D:], bias=bqkv[D:], epi=EPI_BF16)         # K, V of every token
-                    o_r = newr(D)
-                    call("vipant_mha_rows_fwd", q_r.data_ptr(), qkv.data_ptr(), _ptr(ridx), o_r.data_ptr(), probs.data_ptr(), batch, S,
-                         H, int(causal), st)
-                y1_r = gemm_nt(o_r, wo_b, newr(D), bias=bo, epi=EPI_BF16, few_rows=True)
-                x_r = gather_rows(x, ridx, batch, S)
-                # the read-out rows' stream stays fp32 from here, and c_proj adds it in its epilogue: the rows the features are
-                # read from skip the two roundings (fp16 stream, bf16 branch output) the full block would give them
-                x1_r, h2_r, u_r, g_r = newr(D, F32), newr(D), newr(4 * D, torch.uint8), newr(4 * D)
-                mean2_r, rstd2_r = (torch.empty((batch,), dtype=F32, device=dev) for _ in range(2))
-                call("vipant_layernorm_fwd_e4m3", x_r.data_ptr(), D, ln2w.data_ptr(), ln2b.data_ptr(), h2_r.data_ptr(), None,
-                     mean2_r.data_ptr(), rstd2_r.data_ptr(), batch, D, y1_r.data_ptr(), x1_r.data_ptr(), None, None,
-                     _ffi.STREAM_IN_F16 if x_r.dtype == F16 else 0, st)
-                gemm_nt(h2_r, wfc_b, g_r, bias=bfc, aux=u_r, epi=EPI_QUICKGELU_D8, few_rows=True)
-                out_r = gemm_nt(g_r, wpr_b, newr(D, F32), bias=bpr, aux=x1_r, epi=EPI_RESIDUAL_F32, few_rows=True)
-                if train:
-                    saved += [x, mean1, rstd1, h1, qkv, q_r, probs, o_r, h1_r, x1_r, mean2_r, rstd2_r, h2_r, u_r, g_r]
-                x, y_prev = out_r, None
-                continue
-            # ln_1 (+ residual add of the previous block's MLP branch: x <- x + y2_prev) + in_proj
-            xs = new(D, SDT) if y_prev is not None else None
-            call("vipant_ln_qkv_fwd_e4m3", x.data_ptr(), _ptr(y_prev), _ptr(xs), ln1w.data_ptr(), ln1b.data_ptr(), wqkv_b.data_ptr(),
-                 bqkv.data_ptr(), _ptr(h1), mean1.data_ptr(), rstd1.data_ptr(), qkv.data_ptr(), M, D,
-                 C.byref(fp8_plan(q_qkv, None, h1q if (train and keep_q) else act)) if fp8 else None, sflags(x), st)
-            if xs is not None:
-                x = xs
-            # (e4m3: the attention kernel leaves its output's e4m3 form in the activation scratch; out_proj reads it from there)
-            q8 = ((oq if (train and keep_q) else act) if (fp8 and H % 2 == 0 and ATTN_EMIT) else None)
-            o, lse = mha_fwd(qkv, batch, S, H, causal, q8=q8)
-            call("vipant_gemm_bias_residual_fwd_e4m3", None if q8 else o.data_ptr(), wo_b.data_ptr(), bo.data_ptr(), None, y1.data_ptr(),
-                 M, D, D, C.byref(fp8_plan(q_o, None, q8 or act)) if fp8 else None, st)
-            # ln_2 (+ residual add of the attention branch) + c_fc + QuickGELU + c_proj
-            x1 = new(D, SDT)
-            if "gemm_nt" in KERNEL_PROBE and not fp8:     # bench.py times the c_fc launch alone: the same three launches, issued one by one
-                call("vipant_layernorm_fwd_e4m3", x.data_ptr(), D, ln2w.data_ptr(), ln2b.data_ptr(), h2.data_ptr(), None,
-                     mean2.data_ptr(), rstd2.data_ptr(), M, D, y1.data_ptr(), x1.data_ptr(), None, None, sflags(x), st)
-                gemm_nt(h2, wfc_b, g, bias=bfc, aux=u, epi=EPI_QUICKGELU_D8)
-                gemm_nt(g, wpr_b, y2, bias=bpr, epi=EPI_BF16)
-            else:
-                only_q = fp8 and not keep_mlp        # c_proj's operand is all that is wanted of g: neither g nor the codes are written
-                # `recompute_mlp` under e4m3: the LayerNorm output's e4m3 form is kept beside it (M D bytes + scales per block), so
-                # that the backward's c_fc launch needs no quantisation pass either
-                if not (train and keep_q):
-                    h2q = (new(D, torch.uint8), torch.empty((query("vipant_mx_scale_bytes", M, D),), dtype=torch.uint8, device=dev)) if (fp8 and train and recompute_mlp) else None
-                call("vipant_ln_mlp_quickgelu_fwd_e4m3", x.data_ptr(), y1.data_ptr(), x1.data_ptr(), ln2w.data_ptr(), ln2b.data_ptr(),
-                     wfc_b.data_ptr(), bfc.data_ptr(), wpr_b.data_ptr(), bpr.data_ptr(), _ptr(h2), mean2.data_ptr(),
-                     rstd2.data_ptr(), None if only_q else u.data_ptr(), None if (only_q or g is None) else g.data_ptr(), y2.data_ptr(), M, D,
-                     C.byref(fp8_plan(q_fc, q_pr, h2q or act, emit=(gq if (keep_mlp and keep_q) else emit))) if fp8 else None, sflags(x), st)
-            if train:
-                # `recompute_mlp`: the two [M, 4D] MLP activations (16 of the 36 D bytes a block keeps per token) are not
-                # kept; the backward re-runs the c_fc contraction (+1 of a block's 12 contractions) to get them back
-                saved += [x, mean1, rstd1, h1q[0] if keep_q else h1, qkv, o, lse, x1, mean2, rstd2, h2q[0] if keep_q else h2] + \
-                         ([u, gq[0] if keep_q else g] if keep_mlp else [])
-                if fp8 and recompute_mlp:
-                    kept_q.append(h2q)
-                kept_s.append(dict(h1=h1q[1], h2=h2q[1], o=oq, **({"g": gq[1]} if keep_mlp else {})) if keep_q else {})
-            x, y_prev = x1, y2
+                b = _Block(wt=wt, wtq=wtq, wfc_b=wb[2] if s.recompute_mlp else None, q_fc=wq[2] if s.fp8 and s.recompute_mlp else None)
+                x, y_prev = _block_fwd(s, b, x, y_prev, p, wb, wq, tmp)
+            if s.train:
+                blocks.append(b)
         x = residual_add(x, y_prev) if y_prev is not None else x
-        if train:
-            ctx.save_for_backward(*saved, *params)
-            ctx.wts = wts
-            ctx.kept_q = kept_q
-            ctx.kept_s = kept_s
-            ctx.keep_q = keep_q
-            ctx.tn8 = FP8_TN        # (decided by the forward: the backward must read what that forward kept)
-            ctx.meta = (batch, S, bool(causal), L, H, bool(recompute_mlp), fp8, prune)
-            ctx.rows = ridx
-            ctx.last_ctx = ctx_alg
-            ctx.wqkv_b_last = wqkv_b if ctx_alg else None     # bf16 in_proj weight of the last block (its K rows: dq = W_k dqk)
-            ctx.grad_sync = grad_sync
+        if s.train:
+            # the stack's input (version-checked by autograd) and parameters go through autograd; the blocks' own state is the records
+            ctx.save_for_backward(x0, *params)
+            ctx.stack, ctx.blocks, ctx.grad_sync = s, blocks, grad_sync
             ctx._vipant_kind = "stack"
             ctx.readout_grad = None                      # (idx | None, compact fp32 rows), handed over by ReadoutFn.backward
             ctx.patch_node = _producer(x_in, "patch")    # the patch embedding that produced this stack's input, if any
@@ -821,178 +939,61 @@ class BackboneFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dx_in):
-        batch, S, causal, L, H, recompute_mlp, fp8, prune = ctx.meta
-        ridx = ctx.rows
-        tensors = ctx.saved_tensors
-        ns = 11 if recompute_mlp else 13
-        nsaved = ns * (L - 1) + 15 if prune else ns * L
-        saved, params = tensors[:nsaved], tensors[nsaved:]
-        dev = dx_in.device
-        st = _stream()
-        M, D = batch * S, dx_in.shape[1]
+        if ctx.blocks is None:
+            raise _ffi.VipantError("BackboneFn: second backward through the same forward -- the node releases its bf16 weight copies "
+                                   "and saved activations in its first backward (retain_graph re-entry is not supported)")
+        s, blocks, ctx.blocks = ctx.stack, ctx.blocks, None
+        _, *params = ctx.saved_tensors
+        L, M, D, S, dev = len(params) // 12, s.M, s.D, s.S, s.dev
         # Gradient of the residual stream.  Default: bf16 only -- the tensor the next contraction reads IS the stream (LayerNorm
         # backward 10 instead of 16 B per element); the forward stream stays fp32, so the loss and the features are untouched and
         # the gradients move from ~1.3 % to ~1.6 % rel-L2 of the fp32 reference (profiles/r2_stream_precision.md, model D; the
         # reference's own GPU path keeps this stream in fp16).  VIPANT_GRAD_STREAM=fp32: fp32 master + bf16 copy, both in place.
-        if ctx.wts is None:
-            raise _ffi.VipantError("BackboneFn: second backward through the same forward -- the node releases its bf16 weight copies "
-                                   "and saved activations' bookkeeping in its first backward (retain_graph re-entry is not supported)")
         handed, ctx.readout_grad = ctx.readout_grad, None
-        top_rows = None
-        if prune:
+        dx = None
+        if s.prune:
             # the gradient arrives for the read-out rows only, [batch, D]: dense, or handed over by the read-out node
             if handed is not None:
                 dx_in = handed[1] if _is_placeholder(dx_in, handed[2]) else dx_in + handed[1]
-            dx, dx_b = None, None
-            dxr_b = cast_bf16_flat(dx_in.contiguous())
+            dx_b, top = None, cast_bf16_flat(dx_in.contiguous())
         elif handed is not None and _is_placeholder(dx_in, handed[2]) and not GRAD_STREAM_F32:
             # the read-out's gradient as compact rows: they go straight into a zeroed bf16 stream gradient
-            ridx, rows, _ = handed
-            dx = None
+            idx, rows, _ = handed
             dx_b = torch.zeros((M, D), dtype=BF16, device=dev)
-            top_rows = torch.empty((rows.shape[0], D), dtype=BF16, device=dev)
-            call("vipant_scatter_rows_bf16", rows.data_ptr(), _ptr(ridx), dx_b.data_ptr(), top_rows.data_ptr(), rows.shape[0], S, D, st)
+            top = torch.empty((rows.shape[0], D), dtype=BF16, device=dev)
+            call("vipant_scatter_rows_bf16", rows.data_ptr(), _ptr(idx), dx_b.data_ptr(), top.data_ptr(), rows.shape[0], S, D, _stream())
         else:
             if handed is not None:                       # dense gradient from another consumer: add the read-out rows to it
-                ridx, rows, _ = handed
+                idx, rows, _ = handed
                 dx_in = dx_in.contiguous().clone()
-                call("vipant_scatter_rows", rows.data_ptr(), _ptr(ridx), dx_in.data_ptr(), rows.shape[0], S, D, st)
-            if GRAD_STREAM_F32:
-                dx = dx_in.contiguous().clone()
-                dx_b = cast_bf16_flat(dx)
-            else:
-                dx = None
-                dx_b = cast_bf16_flat(dx_in.contiguous())
-        ws = scratch("block_bwd", query("vipant_block_workspace_bytes", M, D), dev)
-        act = emit = dyq = None
-        if fp8:
-            act, emit = fp8_scratch(M, D, dev), fp8_scratch(M, D, dev)
-            if not prune:
-                dyq = quant_e4m3_mx(dx_b)   # from here on every LayerNorm backward leaves the new stream gradient's e4m3 form beside it
+                call("vipant_scatter_rows", rows.data_ptr(), _ptr(idx), dx_in.data_ptr(), rows.shape[0], S, D, _stream())
+            dx = dx_in.contiguous().clone() if GRAD_STREAM_F32 else None
+            dx_b = top = cast_bf16_flat(dx if dx is not None else dx_in.contiguous())
         # scratch shared by all blocks (e4m3 weight gradients: du exists in its e4m3 form alone, in `emit`)
-        du = None if (ctx.keep_q and ctx.tn8) else torch.empty((M, 4 * D), dtype=BF16, device=dev)
-        dh = torch.empty((M, D), dtype=BF16, device=dev)
-        do = torch.empty((M, D), dtype=BF16, device=dev)
-        if recompute_mlp:
-            u = torch.empty((M, 4 * D), dtype=torch.uint8, device=dev)
-            g = None if ctx.keep_q else torch.empty((M, 4 * D), dtype=BF16, device=dev)
-            gq_re = fp8_scratch(M, D, dev) if ctx.keep_q else None
+        tmp = SimpleNamespace(ws=scratch("block_bwd", query("vipant_block_workspace_bytes", M, D), dev), act=None, emit=None)
+        if s.fp8:
+            tmp.act, tmp.emit = fp8_scratch(M, D, dev), fp8_scratch(M, D, dev)
+        # from here on every LayerNorm backward leaves the new stream gradient's e4m3 form beside it
+        dyq = quant_e4m3_mx(dx_b) if (s.fp8 and not s.prune) else None
+        tmp.du, tmp.dh, tmp.do = None if s.keep_q else s.new(4 * D), s.new(D), s.new(D)
+        if s.recompute_mlp:
+            tmp.u, tmp.g = s.new(4 * D, torch.uint8), None if s.keep_q else s.new(4 * D)
+            tmp.gq = mx_buffer(M, 4 * D, dev) if s.keep_q else None
         grads: List[Optional[torch.Tensor]] = [None] * (12 * L)
         lg = _LayerGrads([p.shape for p in params[12 * (L - 1):12 * L]], dev)
         # d c_proj.bias of the top block (lower blocks get theirs from ln_1's backward): column sums of the stream gradient, which
         # with a handed-over read-out gradient has only those rows
-        colsum(dxr_b if prune else (top_rows if top_rows is not None else dx_b), lg.views[11])
+        colsum(top, lg.views[11])
         for l in reversed(range(L)):
-            ln1w, _, _, _, _, _, ln2w, _, _, bfc, _, _ = (p.detach() for p in params[12 * l:12 * l + 12])
-            wqkv_t, wo_t, wfc_t, wpr_t, wfc_b, wq4, wtq4 = ctx.wts[l]
-            (d_ln1w, d_ln1b, d_wqkv, d_bqkv, d_wo, d_bo, d_ln2w, d_ln2b, d_wfc, d_bfc, d_wpr, d_bpr) = lg.views
-            lg_below = _LayerGrads([p.shape for p in params[12 * (l - 1):12 * l]], dev) if l > 0 else None
-            if prune and l == L - 1:
-                # the last block on the read-out rows: the two block operators of the MLP / out_proj half on `batch` rows, the
-                # one-query attention backward, then the K / V half of in_proj and ln_1 on every token
-                x, mean1, rstd1, h1, qkv, q_r, probs, o_r, h1_r, x1_r, mean2_r, rstd2_r, h2_r, u_r, g_r = saved[nsaved - 15:]
-                du_r = torch.empty((batch, 4 * D), dtype=BF16, device=dev)
-                dh_r, do_r, dq_r = (torch.empty((batch, D), dtype=BF16, device=dev) for _ in range(3))
-                call("vipant_ln_mlp_quickgelu_bwd_e4m3", dxr_b.data_ptr(), wpr_t.data_ptr(), wfc_t.data_ptr(), u_r.data_ptr(),
-                     g_r.data_ptr(), h2_r.data_ptr(), x1_r.data_ptr(), mean2_r.data_ptr(), rstd2_r.data_ptr(), ln2w.data_ptr(), None,
-                     dxr_b.data_ptr(), du_r.data_ptr(), dh_r.data_ptr(), d_wpr.data_ptr(), d_wfc.data_ptr(), d_bfc.data_ptr(),
-                     d_ln2w.data_ptr(), d_ln2b.data_ptr(), d_bo.data_ptr(), batch, D, ws.data_ptr(), ws.numel(), None,
-                     (_ffi.STREAM_IN_F16 if x1_r.dtype == F16 else 0) | _ffi.STREAM_FEW_ROWS, st)
-                # out_proj backward on the rows (vipant_gemm_bias_residual_bwd's two launches, the first as a few-rows launch)
-                gemm_nt(dxr_b, wo_t, do_r, epi=EPI_BF16, few_rows=True)
-                gemm_tn(dxr_b, o_r, d_wo, ws_name="block_bwd")
-                if ctx.last_ctx:
-                    wqkv_b_last = ctx.wqkv_b_last
-                    # qkv = [qk | contexts] of the forward.  dctx_h = W_v,h^T do_h; the kernel gives dh of every token and dqk;
-                    # dq_h = W_k,h dqk_h; d W_v = do (x) ctx, d W_k = q (x) dqk per head (block-sparse operands), d b_k = 0
-                    # (qk, the contexts and dqk are bf16 pairs; the two weight gradients take the hi planes: their own rounding, fp32
-                    # sums over `batch * H` bf16 products, is the larger term)
-                    qk, hctx = qkv[0], qkv[1]
-                    dctx = heads_to_wide(do_r, wqkv_t[:, 2 * D:], torch.empty((batch * H, D), dtype=BF16, device=dev), H)
-                    gemm_tn(head_expand(do_r, H), hctx[0], d_wqkv[2 * D:], a_colsum=d_bqkv[2 * D:], ws_name="block_bwd")
-                    dqk = torch.empty((2, batch * H, D), dtype=BF16, device=dev)
-                    call("vipant_rows_ctx_bwd", qk.data_ptr(), dctx.data_ptr(), hctx.data_ptr(), h1.data_ptr(), _ptr(ridx),
-                         probs.data_ptr(), dh.data_ptr(), dqk.data_ptr(), d_bqkv[D:2 * D].data_ptr(), batch, S, H, int(causal), 1, st)
-                    dq_r = wide_to_heads(dqk, wqkv_b_last[D:2 * D], H)
-                    gemm_tn(head_expand(q_r, H), dqk[0], d_wqkv[D:2 * D], ws_name="block_bwd")
-                    del dctx, dqk
-                else:
-                    dqkv = torch.empty((M, 3 * D), dtype=BF16, device=dev)
-                    call("vipant_mha_rows_bwd", q_r.data_ptr(), qkv.data_ptr(), _ptr(ridx), probs.data_ptr(), do_r.data_ptr(),
-                         dq_r.data_ptr(), dqkv.data_ptr(), batch, S, H, int(causal), st)
-                    # dh = dK|dV . W_kv on every token
-                    gemm_nt(dqkv[:, D:], wqkv_t[:, D:], dh, epi=EPI_BF16)
-                    gemm_tn(dqkv[:, D:], h1, d_wqkv[D:], a_colsum=d_bqkv[D:], ws_name="block_bwd")
-                    del dqkv
-                # + dq . W_q on the read-out rows
-                dhq = gemm_nt(dq_r, wqkv_t[:, :D], torch.empty((batch, D), dtype=F32, device=dev), epi=EPI_F32, few_rows=True)
-                call("vipant_add_rows_bf16", dh.data_ptr(), _ptr(ridx), dhq.data_ptr(), 1, batch, S, D, st)
-                gemm_tn(dq_r, h1_r, d_wqkv[:D], a_colsum=d_bqkv[:D], ws_name="block_bwd")
-                # ln_1 backward on every token; the residual gradient of this block exists on the read-out rows only
-                dx_b = torch.empty((M, D), dtype=BF16, device=dev)
-                call("vipant_layernorm_bwd_e4m3", dh.data_ptr(), _ffi.LN_X_F16 if x.dtype == F16 else 0, x.data_ptr(), D,
-                     mean1.data_ptr(), rstd1.data_ptr(), ln1w.data_ptr(), None, None, D, dx_b.data_ptr(), d_ln1w.data_ptr(),
-                     d_ln1b.data_ptr(), lg_below.views[11].data_ptr() if lg_below is not None else None, 0, M, D, ws.data_ptr(),
-                     ws.numel(), None, None, st)
-                call("vipant_add_rows_bf16", dx_b.data_ptr(), _ptr(ridx), dxr_b.data_ptr(), 0, batch, S, D, st)
-                if lg_below is not None:
-                    colsum(dxr_b, lg_below.views[11], accumulate=True)
-                if GRAD_STREAM_F32:
-                    dx = torch.empty((M, D), dtype=F32, device=dev)
-                    call("vipant_cast_f32", dx_b.data_ptr(), dx.data_ptr(), M * D, st)
-                if fp8:
-                    dyq = quant_e4m3_mx(dx_b)
-                for i, v in enumerate(lg.views):
-                    grads[12 * l + i] = v
-                if ctx.grad_sync is not None:
-                    ctx.grad_sync.reduce_async(lg.flat, lg.views, params[12 * l:12 * l + 12])
-                lg = lg_below
-                continue
-            x, mean1, rstd1, h1, qkv, o, lse, x1, mean2, rstd2, h2 = saved[ns * l:ns * l + 11]
-            kq = ctx.keep_q          # h1, h2 (and g) are the e4m3 forms the forward kept; their block scales are in ctx.kept_s
-            if recompute_mlp:
-                h2q = ctx.kept_q[l] if fp8 else None
-                # (e4m3 weight gradients: the recomputation leaves g's e4m3 form -- the same epilogue, the same bytes as a forward that
-                # keeps it -- and no bf16 g)
-                call("vipant_mlp_quickgelu_recompute_e4m3", None if fp8 else h2.data_ptr(), wfc_b.data_ptr(), bfc.data_ptr(), u.data_ptr(),
-                     None if kq else g.data_ptr(), M, D, C.byref(fp8_plan(wq4[2], None, h2q, emit=gq_re if kq else None)) if fp8 else None, st)
-                if fp8:
-                    ctx.kept_q[l] = None
-                keep = gq_re if kq else None
+            p = [t.detach() for t in params[12 * l:12 * l + 12]]
+            lg_below = _LayerGrads([t.shape for t in params[12 * (l - 1):12 * l]], dev) if l > 0 else None
+            # (a record leaves `blocks` here: it is dropped when its block's backward returns)
+            if s.prune and l == L - 1:
+                dx, dx_b, dyq = _rows_block_bwd(s, blocks.pop(), p, lg, lg_below, top, tmp)
             else:
-                u, g = saved[ns * l + 11:ns * l + 13]
-                keep = (g, ctx.kept_s[l]["g"]) if kq else None
-            keep2 = (h2, ctx.kept_s[l]["h2"]) if kq else None
-            keep1 = (h1, ctx.kept_s[l]["h1"]) if kq else None
-            # MLP half: c_proj^T + QuickGELU', c_fc^T, both weight gradients, ln_2 backward (+ residual gradient);
-            # the produced stream gradient is also d(out_proj output): its column sum is d out_proj.bias
-            call("vipant_ln_mlp_quickgelu_bwd_e4m3", dx_b.data_ptr(), wpr_t.data_ptr(), wfc_t.data_ptr(), u.data_ptr(),
-                 None if keep else g.data_ptr(),
-                 None if keep2 else h2.data_ptr(), x1.data_ptr(), mean2.data_ptr(), rstd2.data_ptr(), ln2w.data_ptr(), _ptr(dx), dx_b.data_ptr(),
-                 _ptr(du), dh.data_ptr(), d_wpr.data_ptr(), d_wfc.data_ptr(), d_bfc.data_ptr(), d_ln2w.data_ptr(),
-                 d_ln2b.data_ptr(), d_bo.data_ptr(), M, D, ws.data_ptr(), ws.numel(),
-                 C.byref(fp8_plan(wtq4[3], wtq4[2], act, dyq, emit=emit, tn=ctx.tn8, keep=keep, keep2=keep2)) if fp8 else None,
-                 _ffi.STREAM_IN_F16 if x1.dtype == F16 else 0, st)
-            # attention half: out_proj^T, attention core, in_proj^T + ln_1 backward; the produced stream gradient is
-            # d(c_proj output) of the block below: its column sum is that block's d c_proj.bias
-            call("vipant_gemm_bias_residual_bwd_e4m3", dx_b.data_ptr(), wo_t.data_ptr(), o.data_ptr(), do.data_ptr(), d_wo.data_ptr(),
-                 M, D, D, ws.data_ptr(), ws.numel(),
-                 C.byref(fp8_plan(wtq4[1], None, act, dyq, emit=emit, tn=ctx.tn8, keep=ctx.kept_s[l]["o"] if kq else None)) if fp8 else None, st)
-            q8 = act if (fp8 and H % 2 == 0 and ATTN_EMIT) else None
-            dqkv = mha_bwd(qkv, o, do, lse, batch, S, H, causal, q8=q8)
-            call("vipant_ln_qkv_bwd_e4m3", dqkv.data_ptr(), wqkv_t.data_ptr(), None if keep1 else h1.data_ptr(), x.data_ptr(), mean1.data_ptr(),
-                 rstd1.data_ptr(), ln1w.data_ptr(), _ptr(dx), dx_b.data_ptr(), dh.data_ptr(), d_wqkv.data_ptr(),
-                 d_bqkv.data_ptr(), d_ln1w.data_ptr(), d_ln1b.data_ptr(),
-                 lg_below.views[11].data_ptr() if lg_below is not None else None, M, D, ws.data_ptr(), ws.numel(),
-                 C.byref(fp8_plan(wtq4[0], None, act, dyq, emit=emit, tn=ctx.tn8, keep=keep1)) if fp8 else None,
-                 (_ffi.STREAM_IN_F16 if x.dtype == F16 else 0) | (_ffi.STREAM_ACT_Q if q8 else 0), st)
-            del dqkv
-            for i, v in enumerate(lg.views):
-                grads[12 * l + i] = v
-            if ctx.grad_sync is not None:
-                ctx.grad_sync.reduce_async(lg.flat, lg.views, params[12 * l:12 * l + 12])
+                _block_bwd(s, blocks.pop(), p, lg, lg_below, dx, dx_b, dyq, tmp)
+            lg.publish(grads, l, params, ctx.grad_sync)
             lg = lg_below
-        ctx.wts = ctx.wqkv_b_last = ctx.kept_q = ctx.kept_s = None
         need = ctx.needs_input_grad
         patch = ctx.patch_node                      # kept: a second backward over a retained graph hands over again
         if dx is None and need[0]:
@@ -1001,7 +1002,7 @@ class BackboneFn(torch.autograd.Function):
                 patch.stream_grad = (dx_b, dx)      # (whatever an earlier, never-consumed hand-off left there is replaced)
             else:
                 dx = torch.empty((M, D), dtype=F32, device=dev)
-                call("vipant_cast_f32", dx_b.data_ptr(), dx.data_ptr(), M * D, st)
+                call("vipant_cast_f32", dx_b.data_ptr(), dx.data_ptr(), M * D, _stream())
         out_grads = [gr if need[9 + i] else None for i, gr in enumerate(grads)]
         return (dx if need[0] else None, None, None, None, None, None, None, None, None, *out_grads)
 
@@ -1021,8 +1022,7 @@ class ReadoutFn(torch.autograd.Function):
         train = any(ctx.needs_input_grad)
         rows = torch.empty((batch, D), dtype=F32, device=dev) if idx is not None else None
         y = torch.empty((batch, D), dtype=BF16, device=dev)
-        mean = torch.empty((batch,), dtype=F32, device=dev)
-        rstd = torch.empty((batch,), dtype=F32, device=dev)
+        mean, rstd = _stats(batch, dev)
         if train:
             proj_b, proj_t = cast_bf16(proj.detach(), True)
         else:
@@ -1238,8 +1238,7 @@ def batchnorm_fwd(x: torch.Tensor, gamma=None, beta=None, *, relu: bool = False,
     _need(x, F32, "batchnorm_fwd.x")
     M, N = x.shape
     y = torch.empty((M, N), dtype=BF16, device=x.device)
-    mean = torch.empty((N,), dtype=F32, device=x.device)
-    rstd = torch.empty((N,), dtype=F32, device=x.device)
+    mean, rstd = _stats(N, x.device)
     ws = scratch("batchnorm", query("vipant_batchnorm_workspace_bytes", M, N), x.device)
     call("vipant_batchnorm_fwd", x.data_ptr(), x.stride(0), _ptr(gamma), _ptr(beta), int(relu), y.data_ptr(), mean.data_ptr(),
          rstd.data_ptr(), _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked), float(momentum), float(eps), M, N,
