@@ -380,6 +380,30 @@ size_t vipant_barlow_loss_workspace_bytes(int64_t N);
 int32_t vipant_barlow_loss(const float* c, int64_t ldc, int64_t M, float lambd, float* loss, const float* grad_scale, uint16_t* G,
                            uint16_t* Gt, int64_t N, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ==== Classification loss heads (vipant_amd/csrc/classify.hip) ==============================================================
+ * Both take the UNSCALED fp32 logits z [B, ldz] (C <= ldz valid columns) of the head's last Linear and the log temperature
+ * `logit_scale` (device fp32 scalar), score rows [row0, row0 + nrows) and write, in one pass over a row held by one wave:
+ * loss fp32 [1] = the sum of the scored rows' terms over the FULL denominator (B, or B * C), so the losses of disjoint row
+ * ranges add up to the whole batch's; dz bf16 [B, ldd] (optional; scored rows only) = grad_scale * d loss / d z with columns
+ * C .. ldd-1 written as zeros (the class dimension padded for the contractions); dscale fp32 [1] (optional) = grad_scale *
+ * d loss / d logit_scale (the parameter is the log: the factor exp(logit_scale) is included).  Deterministic: fixed-order
+ * two-level reductions through `workspace` (vipant_*_workspace_bytes(nrows)), no float atomics.
+ *
+ * vipant_softmax_ce: nn.CrossEntropyLoss()(exp(ls) * z, labels), cvap/module/decoder/loss_head.py:416-418.  labels int64 [B] on
+ * the device; a label outside [0, C) cannot be seen by the host and is clamped into the range by the kernel.  pred int32 [B]
+ * (optional) = arg-max column, the lowest index on exact ties (torch.argmax, loss_head.py:356-357).
+ * vipant_bce_logits: nn.BCEWithLogitsLoss()(exp(ls) * z, targets), cvap/module/decoder/loss_more.py:66-69, 140-142, in the
+ * overflow-safe max(x, 0) - x t + log1p(exp(-|x|)) form.  targets uint8 [B, ldt] (non-zero = 1); logit_scale may be NULL
+ * (scale 1: `scaling: False`; dscale must then be NULL); prob fp32 [B, ldp] (optional) = sigmoid(exp(ls) * z). */
+size_t vipant_softmax_ce_workspace_bytes(int64_t nrows);
+int32_t vipant_softmax_ce(const float* z, int64_t ldz, const int64_t* labels, const float* logit_scale, float* loss, uint16_t* dz,
+                          int64_t ldd, float* dscale, int32_t* pred, int64_t row0, int64_t nrows, float grad_scale, int64_t B,
+                          int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+size_t vipant_bce_logits_workspace_bytes(int64_t nrows);
+int32_t vipant_bce_logits(const float* z, int64_t ldz, const uint8_t* targets, int64_t ldt, const float* logit_scale, float* loss,
+                          uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp, int64_t row0, int64_t nrows,
+                          float grad_scale, int64_t B, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ==== The fused operator set: one entry point per reference operator group, forward and backward ==========
  * Host-side compositions of the kernels above (vipant_amd/csrc/block.hip): same stream, no allocation, no synchronisation.
  * Fusion plan: a residual add rides on the NEXT LayerNorm pass (`add` bf16 [M,D] = the previous branch output, `x_out` fp32

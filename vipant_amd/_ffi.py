@@ -130,6 +130,11 @@ PROTOTYPES = {
     "vipant_batchnorm_bwd": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _p, _i32, _p, _p, _p, _i64, _i64, _i32, _i64, _i64, _p, _sz, _p]),
     "vipant_barlow_loss_workspace_bytes": (_sz, [_i64]),
     "vipant_barlow_loss": (_i32, [_p, _i64, _i64, _f32, _p, _p, _p, _p, _i64, _p, _sz, _p]),
+    # classification loss heads (vipant_amd/csrc/classify.hip)
+    "vipant_softmax_ce_workspace_bytes": (_sz, [_i64]),
+    "vipant_softmax_ce": (_i32, [_p, _i64, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
+    "vipant_bce_logits_workspace_bytes": (_sz, [_i64]),
+    "vipant_bce_logits": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
 }
 
 

@@ -43,6 +43,19 @@ GROUPS = {
             "batch_size": 64, "force_npz": False, "clf": False, "np_rnd": False, "mixup_rate": 0.0,
             "weighted_sampling": False, "siamese": dict(_siamese),
         }),
+        # supervised audio classification (configs/running/esc50.yaml, us8k.yaml): 5- / 10-fold cross validation.  The reference's
+        # us8k.yaml has no `excl_modules`, which ESClassifier.build reads; both groups carry it here.  `synthetic_folds` /
+        # `synthetic_classes`: the dataset-free x-fold loader of ESCMonitor (50 classes for ESC-50, 10 for UrbanSound8K)
+        "esc50": dict(_running_common, **{
+            "prompt": "the sound of ", "data_name": "esc50", "zero_shot": False, "eval_name": "", "test_name": "",
+            "eval_samples": 5000, "test_samples": 5000, "peep_rate": 16, "save_rate": 1e9, "batch_size": 50, "epochs": 32,
+            "save_epoch": True, "excl_modules": {"amodules": []}, "synthetic_folds": 2, "synthetic_classes": 50,
+        }),
+        "us8k": dict(_running_common, **{
+            "prompt": "the sound of ", "data_name": "UrbanSound8K", "zero_shot": False, "eval_name": "", "test_name": "",
+            "eval_samples": 5000, "test_samples": 5000, "peep_rate": 50, "save_rate": 1e9, "batch_size": 50, "epochs": 32,
+            "save_epoch": True, "excl_modules": {"amodules": []}, "synthetic_folds": 2, "synthetic_classes": 10,
+        }),
     },
     "running/audio": {
         "default": {
@@ -96,6 +109,10 @@ GROUPS = {
         "barlow_ce": {"name": "BarlowCELossHead", "lambd_barlow": 0.05, "ce": {"name": "CELossHead"},
                       "barlow": {"name": "BarlowLossHead", "embed_dim": "${model.image.embed_dim}", "lambd_off": 0.0051,
                                  "layers": [2048, 4096, 4096]}},
+        # configs/model/loss/ce_cls.yaml, bce.yaml (the class count arrives as `output_dim` from the trainer)
+        "ce_cls": {"name": "ClassificationHead", "embed_dim": "${model.image.embed_dim}", "layers": [], "scaling": True},
+        "bce": {"name": "BCELossHead", "embed_dim": "${model.audio.embed_dim}", "width": "${model.audio.width}", "layers": [],
+                "scaling": True, "bias": False},
     },
     "optimizer": {
         "standard": {

@@ -12,7 +12,7 @@ from .heads import (  # noqa: F401
 )
 from .loss_head import (  # noqa: F401
     LOSS_HEADS_REGISTRY, build_loss_head, LossHead, CELossHead, VALCELossHead, BarlowLossHead, BarlowCELossHead, DummyLossHead,
-    zero_shot_report,
+    ClassificationHead, BCELossHead, zero_shot_report,
 )
 
 LOSS_HEADS_REGISTRY._do_register("DummyHead", DummyLossHead)

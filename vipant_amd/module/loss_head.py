@@ -378,6 +378,184 @@ class BarlowCELossHead(LossHead):
         return loss_ce + self.lambd_barlow * loss_barlow
 
 
+def _classifier_widths(who, sizes):
+    """Every width of a classification head feeds a LayerNorm and is the K of a contraction: a positive multiple of 64 for
+    vipant_gemm_nt, and a multiple of 256 up to 1024 for the library's LayerNorm kernels."""
+    for name, w in [("embed_dim", sizes[0])] + [(f"layers[{i}]", v) for i, v in enumerate(sizes[1:])]:
+        if w <= 0 or w % 64:
+            raise VipantError(f"{who}: {name} = {w} is not a positive multiple of 64 (the head's contractions need K % 64 == 0)")
+        if w % 256 or w > 1024:
+            raise VipantError(f"{who}: {name} = {w} is not a multiple of 256 up to 1024 (the widths the LayerNorm kernels take)")
+
+
+class _ClassifierHead(LossHead):
+    """What ClassificationHead and BCELossHead share: `linear` = [LayerNorm, Linear] pairs under the reference's names, the
+    training forward through ops.ClassifierFn, the eval forward on rank 0 only."""
+
+    kind = "ce"
+
+    def _build_linear(self, sizes, last_bias=True):
+        from .val import LayerNorm
+        _classifier_widths(type(self).__name__, sizes[:-1])
+        if int(sizes[-1]) < 1:
+            raise VipantError(f"{type(self).__name__}: output_dim = {sizes[-1]} classes")
+        layers = []
+        for i in range(len(sizes) - 1):
+            layers.extend([LayerNorm(sizes[i]), nn.Linear(sizes[i], sizes[i + 1], bias=(last_bias if i == len(sizes) - 2 else True))])
+        self.linear = nn.Sequential(*layers)
+        self.nclass = int(sizes[-1])
+
+    def _params(self):
+        mods = list(self.linear)
+        out = []
+        for ln, lin in zip(mods[0::2], mods[1::2]):
+            out += [ln.weight, ln.bias, lin.weight, lin.bias]
+        return out
+
+    def _scale(self, device):
+        if isinstance(self.logit_scale, nn.Parameter):
+            return self.logit_scale
+        return self.logit_scale.to(device) if self.scaling else None
+
+    def _target(self, x2, device):
+        if self.kind == "ce":
+            return torch.as_tensor(x2, device=device).long().contiguous()
+        x2 = torch.as_tensor(x2, device=device)
+        return (x2 if x2.dtype == torch.uint8 else (x2 != 0).to(torch.uint8)).contiguous()      # multi-hot: binary targets
+
+    def _run(self, x1, x2, **meta_kwargs):
+        params = self._params()
+        ls = self._scale(x1.device)
+        if not torch.is_grad_enabled():
+            params = [None if p is None else p.detach() for p in params]     # nothing will be differentiated: forward-only path
+            ls = None if ls is None else ls.detach()
+        grad_scale = 1.0 / parallel.world_size() if (parallel.active() and self.training) else 1.0
+        meta = ops.ClassifierMeta(self.kind, self.nclass, grad_scale, **meta_kwargs)
+        loss = ops.ClassifierFn.apply(x1.float(), self._target(x2, x1.device), ls, meta, *params)
+        return loss, meta
+
+    def forward(self, x1, x2, *args, **kwargs):
+        """x1: features fp32 [b, E]; x2: labels int [b] (ClassificationHead) or multi-hot targets [b, C] (BCELossHead).  Under
+        replicas a rank scores its own rows -- the loss is a mean of per-sample terms, no gather is needed -- and every gradient
+        leaves the kernel scaled by 1 / world: the replicas SUM-reduce the head's parameter gradients with the tower's."""
+        if not self.training:
+            if not dist.is_initialized() or dist.get_rank() == 0:
+                return self.infer(x1, x2, *args, **kwargs)
+            return None
+        return self._run(x1, x2)[0]
+
+
+@LOSS_HEADS_REGISTRY.register()
+class ClassificationHead(_ClassifierHead):
+    """Soft-max classifier on audio features (cvap/module/decoder/loss_head.py:330-419): LayerNorm + Linear under `linear.0` /
+    `linear.1`, a learnable temperature, nn.CrossEntropyLoss.  Training: ops.ClassifierFn.  Eval: `infer` caches features,
+    arg-max predictions (the loss kernel's `pred`) and labels; `report` is the supervised precision or, with `text`, the
+    zero-shot one (zero_shot_report)."""
+
+    kind = "ce"
+
+    def __init__(self, cfg, **kwargs):
+        super().__init__()
+        self.normalized = False
+        if "output_dim" not in kwargs:
+            raise VipantError("ClassificationHead: `the label number` is not found in `kwargs` (output_dim)")
+        self._build_linear([int(cfg.embed_dim), int(kwargs["output_dim"])])
+        self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
+        self.scaling = True
+        self.reduce = False
+
+    def copy_state_dict(self, state_dict):
+        new_dict = self.state_dict()
+        new_dict.update({k: v for k, v in state_dict.items() if k in new_dict})
+        self.load_state_dict(new_dict)
+
+    def infer(self, x1, x2, *args, **kwargs):
+        if not hasattr(self, "audios") or not hasattr(self, "x1s") or not hasattr(self, "x2s") or not hasattr(self, "ids"):
+            self.audios, self.x1s, self.x2s, self.ids = [], [], [], []
+        with torch.no_grad():
+            _, meta = self._run(x1.detach(), x2, want_pred=True)
+        self.audios.append(x1.detach().float())
+        self.x1s.append(meta.pred.long())
+        self.x2s.append(torch.as_tensor(x2, device=x1.device).long())
+        names = kwargs.get("names", None)
+        if names is not None:
+            self.ids.extend(names)
+        return None
+
+    def report(self, gold_file=None, **kwargs):
+        x1s, x2s = torch.cat(self.x1s), torch.cat(self.x2s)
+        nsample = len(x1s)
+        text = kwargs.get("text", None)
+        if text is not None:
+            out = zero_shot_report(torch.cat(self.audios), x2s, text, kwargs.get("label_map", None))
+        else:
+            precision = (x1s == x2s).sum() / nsample * 100.       # float32 tensor, as in the reference
+            out = f"A->T: p1 = {precision:2.2f} @ {nsample}"
+        del self.audios, self.x1s, self.x2s, self.ids
+        return out
+
+
+@LOSS_HEADS_REGISTRY.register()
+class BCELossHead(_ClassifierHead):
+    """Multi-label tagging head (cvap/module/decoder/loss_more.py:29-143): `cfg.layers` hidden widths give LayerNorm / Linear
+    pairs `linear.{2i}` / `linear.{2i+1}`, the last Linear has `bias=cfg.bias`; nn.BCEWithLogitsLoss on exp(logit_scale) x logits
+    (`scaling: False`: a plain tensor of 0, scale 1).  Eval: `infer` returns the loss and caches the sigmoid scores; `report`
+    is the reference's string with its scikit-learn quantities restated in numpy (vipant_amd/util/metrics.py)."""
+
+    kind = "bce"
+
+    def __init__(self, cfg, **kwargs):
+        super().__init__()
+        self.normalized = False
+        if "output_dim" not in kwargs:
+            raise VipantError("BCELossHead: `the label number` is not found in `kwargs` (output_dim)")
+        embed_dim = cfg.embed_dim or cfg.width
+        self._build_linear([int(embed_dim)] + [int(w) for w in cfg.layers] + [int(kwargs["output_dim"])], last_bias=bool(cfg.bias))
+        self.scaling = bool(cfg.scaling)
+        self.logit_scale = (nn.Parameter(torch.ones([]) * np.log(1 / 0.07)) if cfg.scaling
+                            else torch.ones([], requires_grad=False) * np.log(1 / 1))
+        self.reduce = False
+
+    def copy_state_dict(self, state_dict):
+        key = "logit_scale"
+        new_dict = self.state_dict()
+        new_dict.update({key: state_dict[key]})
+        self.load_state_dict(new_dict)
+
+    def infer(self, x1, x2, *args, **kwargs):
+        if not hasattr(self, "audios") or not hasattr(self, "x1s") or not hasattr(self, "x2s") or not hasattr(self, "ids"):
+            self.audios, self.x1s, self.x2s, self.ids = [], [], [], []
+        with torch.no_grad():
+            loss, meta = self._run(x1.detach(), x2, want_prob=True)
+        self.audios.append(x1.detach().float())
+        self.x1s.append(meta.prob)
+        self.x2s.append(torch.as_tensor(x2, device=x1.device))
+        names = kwargs.get("names", None)
+        if names is not None:
+            self.ids.extend(names)
+        return loss
+
+    def zero_shot(self, text, gold_file):
+        audios = ops.l2_normalize(torch.cat(self.audios).contiguous())
+        text = ops.l2_normalize(text.detach().float().contiguous())
+        x1s = torch.empty((audios.shape[0], text.shape[0]), dtype=torch.float32, device=audios.device)
+        a16, t16 = ops.cast_bf16(audios)[0], ops.cast_bf16(text)[0]
+        if text.shape[0] % 4:
+            raise VipantError(f"BCELossHead.zero_shot: {text.shape[0]} prompts; the similarity contraction needs a multiple of 4")
+        ops.gemm_nt(a16, t16, x1s, epi=ops.EPI_F32)
+        return self.report(gold_file=gold_file, text=None, x1s=x1s.cpu().numpy())
+
+    def report(self, gold_file=None, x1s=None, x2s=None, **kwargs):
+        from ..util.metrics import multilabel_report
+        text = kwargs.get("text", None)
+        if text is not None:
+            return self.zero_shot(text, gold_file)
+        x1s = torch.cat(self.x1s).cpu().numpy() if x1s is None else x1s
+        x2s = torch.cat(self.x2s).cpu().numpy() if x2s is None else x2s
+        del self.audios, self.x1s, self.x2s, self.ids
+        return multilabel_report(x2s, x1s)
+
+
 class DummyLossHead(nn.Module):
     def __init__(self, cfg, **kwargs):
         super().__init__()

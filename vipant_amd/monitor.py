@@ -88,15 +88,23 @@ class Monitor(object):
         negatives = cfg.running.get("negatives", "global")
         tunable_params = model.build(negatives=negatives)
         self.model = model
+        self._configure(model)
+        self.model.train(not cfg.eval)
+        self.build_optimizer(tunable_params)
+
+    def _configure(self, model):
+        """Run-time switches of the towers (`running.*`) and, under replicas, the gradient reduction they feed."""
+        cfg = self.cfg
+        towers = (model.audio_head, getattr(model, "image_head", None), getattr(model, "text_head", None))
         self.grad_sync = None
         if parallel.active():
             # `running.comm_overlap`: block (default: each block's bucket is reduced while the blocks below run their backward) | step
             self.grad_sync = parallel.GradSync(overlap=str(cfg.running.get("comm_overlap", "block")))
-            for head in (model.audio_head, model.image_head, model.text_head):
+            for head in towers:
                 if head is not None and hasattr(head, "encoder"):
                     head.encoder.grad_sync = self.grad_sync
         if cfg.running.get("recompute_mlp", False):
-            for head in (model.audio_head, model.image_head, model.text_head):
+            for head in towers:
                 if head is not None and hasattr(head, "encoder"):
                     head.encoder.recompute_mlp = True
         if cfg.running.get("grad_stream", None) is not None:        # bf16 (default) | fp32 master of the stream gradient
@@ -108,15 +116,13 @@ class Monitor(object):
         # `running.last_block_rows` (default on): a tower's last block is evaluated on the rows its read-out takes (class / end-of-text
         # token) -- exact, see ops.BackboneFn; off: the full block, as the reference computes it before discarding the other rows
         last_rows = bool(cfg.running.get("last_block_rows", True)) and os.environ.get("VIPANT_LAST_BLOCK_ROWS", "1") != "0"
-        for head in (model.audio_head, model.image_head, model.text_head):
+        for head in towers:
             if head is not None and hasattr(head, "encoder"):
                 head.encoder.stream_f16 = stream_f16
                 head.encoder.last_block_rows = last_rows
         if cfg.running.get("fp8_gemm", False):      # BASELINE.json configs[4]: e4m3 operands in the audio tower's NT contractions
             if model.audio_head is not None and hasattr(model.audio_head, "encoder"):
                 model.audio_head.encoder.fp8 = True
-        self.model.train(not cfg.eval)
-        self.build_optimizer(tunable_params)
 
     def build_data(self):
         rcfg = self.cfg.running
@@ -319,7 +325,7 @@ class Monitor(object):
         ntune = sum(p.numel() for p in self.model.parameters() if p.requires_grad)
         self.echo(f"# param {ntotal / 1e6:.2f}M # tunable {ntune / 1e6:.2f}M.")
         # transformer-stack parameters are reduced per layer by the backward itself (parallel.GradSync)
-        for head in (self.model.audio_head, self.model.image_head, self.model.text_head):
+        for head in (self.model.audio_head, getattr(self.model, "image_head", None), getattr(self.model, "text_head", None)):
             if head is not None and hasattr(head, "encoder"):
                 for p in head.encoder.parameters():
                     p._vipant_bucketed = True
@@ -360,4 +366,263 @@ class VAMonitor(Monitor):
     with_text = False
 
 
-__all__ = ["Monitor", "VAMonitor", "VALMonitor", "SyntheticLoader"]
+class SyntheticFolds:
+    """Labelled x-fold data with the contract of the reference's ESC-50 / UrbanSound8K collator (cvap/data/esc50.py): batches of
+    (audios [b, T, F] fp32, labels int64 [b], names).  Dataset-free and seeded: sample i of a fold has class i mod C and the
+    spectrogram `prototype[class] + noise`, so the classes are separable and a classifier can be seen to learn.  `loader_list`
+    holds, per fold, (train loader factory over the other folds -- reshuffled every epoch --, eval loader factory over the fold
+    held out), as `build_xfold_dataloader_list` returns them; under replicas a rank takes every world-th training batch."""
+
+    class _Loader:
+        def __init__(self, owner, folds, batch, shuffle, shard):
+            self.owner, self.folds, self.b, self.shuffle, self.shard = owner, list(folds), int(batch), shuffle, shard
+            self.index = [(f, i) for f in self.folds for i in range(owner.per_fold)]
+            self.epoch = 0
+            nb = len(self.index) // self.b if shuffle else -(-len(self.index) // self.b)
+            self.nbatch = nb // shard[1] if shard[1] > 1 else nb
+
+        def __len__(self):
+            return self.nbatch
+
+        def __iter__(self):
+            order = list(range(len(self.index)))
+            if self.shuffle:
+                g = torch.Generator().manual_seed(self.owner.seed + 7919 * self.epoch + 31 * sum(self.folds))
+                order = torch.randperm(len(order), generator=g).tolist()
+                self.epoch += 1
+            rank, world = self.shard
+            for ib in range(self.nbatch):
+                k = ib * world + rank if world > 1 else ib
+                picks = [self.index[j] for j in order[k * self.b:(k + 1) * self.b]]
+                yield self.owner.batch(picks)
+
+    def __init__(self, cfg, nfold, nclass, per_fold, shard=(0, 1)):
+        rcfg = cfg.running
+        self.seed, self.nfold, self.nclass, self.per_fold = int(cfg.seed), int(nfold), int(nclass), int(per_fold)
+        self.T, self.F = int(rcfg.max_audio_len), int(rcfg.num_mel_bins)
+        g = torch.Generator().manual_seed(self.seed)
+        self.proto = torch.randn(self.nclass, self.T, self.F, generator=g)
+        b = int(rcfg.batch_size)
+        every = list(range(self.nfold))
+        self.loader_list = [
+            ((lambda k=k: (None, self._Loader(self, [f for f in every if f != k] or [k], b, True, shard))),
+             (lambda k=k: (None, self._Loader(self, [k], b, False, (0, 1)))))
+            for k in every]
+        self.lid2str = [f"class {c}" for c in range(self.nclass)]
+        g = torch.Generator().manual_seed(self.seed + 1)
+        self.lid2int = []                       # one tokenised prompt per class (`running.prompt` + label): SOT, ids, EOT
+        for c in range(self.nclass):
+            n = int(torch.randint(3, 8, (1,), generator=g))
+            self.lid2int.append([SOT] + torch.randint(1, SOT, (n,), generator=g).tolist() + [EOT])
+        width = max(len(t) for t in self.lid2int)
+        self.lid2int = [t + [0] * (width - len(t)) for t in self.lid2int]
+        self.label_map = None
+
+    def batch(self, picks):
+        labels = torch.tensor([i % self.nclass for _, i in picks], dtype=torch.int64)
+        audios = torch.empty(len(picks), self.T, self.F)
+        for n, (f, i) in enumerate(picks):
+            g = torch.Generator().manual_seed(self.seed + 100003 * (f + 1) + i)
+            audios[n] = self.proto[i % self.nclass] + torch.randn(self.T, self.F, generator=g)
+        return audios, labels, [f"synthetic-fold{f}-{i}" for f, i in picks]
+
+
+class ESCMonitor(Monitor):
+    """x-fold supervised classification trainer (cvap/monitor/esc50_clf.py:24-386; `monitor=ESCMonitor`, `running=esc50` /
+    `us8k`): per fold a fresh model is trained for `optimizer.epochs` epochs and evaluated on the held-out fold after every
+    epoch; `summary_report` prints the best-epoch and per-fold-maximum precision statistics.  `eval=True running.zero_shot=True`
+    classifies every fold by the text tower's prompt features instead.  AMP's GradScaler (esc50_clf.py:88, 179-183) has no
+    counterpart: bf16 operands with fp32 accumulation and fp32 master weights need no loss scaling."""
+
+    def __init__(self, cfg, echo, device, loader_list=None):
+        self.cfg, self.echo, self.device = cfg, echo, device
+        self.dataloader = self.evalloader = self.testloader = None
+        self.gold_file = None
+        output_dim = self.build_data(loader_list)
+        self._build_model(output_dim)
+
+    def _build_model(self, output_dim):
+        model = build_main_model(self.cfg, self.echo)
+        tunable_params = model.build(output_dim=output_dim)
+        self.model = model
+        self._configure(model)
+        self.model.train(not self.cfg.eval)
+        self.build_optimizer(tunable_params)
+
+    def reinitialize(self, cfg, echo):
+        self.echo("Reinitialize everything except `dataloader_list`.")
+        self._build_model(len(self.lid2str))
+
+    def build_data(self, loader_list=None):
+        rcfg = self.cfg.running
+        if loader_list is not None:
+            self.loader_list, self.lid2str, self.lid2int, self.label_map = loader_list
+            return len(self.lid2str)
+        shard = (parallel.rank(), parallel.world_size()) if parallel.active() else (0, 1)
+        data = SyntheticFolds(self.cfg, rcfg.get("synthetic_folds", 2), rcfg.get("synthetic_classes", 50),
+                              int(rcfg.get("synthetic_steps", 8)) * int(rcfg.batch_size), shard)
+        self.loader_list, self.lid2str, self.lid2int, self.label_map = data.loader_list, data.lid2str, data.lid2int, data.label_map
+        self.echo(f"Instantiate {len(self.loader_list)}-fold dataloaders from `synthetic': {data.per_fold} samples per fold, "
+                  f"{len(self.lid2str)} classes.")
+        return len(self.lid2str)
+
+    # ------------------------------------------------------------------ esc50_clf.py:58-102
+    def learn(self):
+        if not self.model.training:
+            if self.cfg.running.get("zero_shot", False):
+                self.echo("(Zero-shot) Evaluating started...")
+                with torch.no_grad():
+                    report = self.standard_zero_shot()
+                self.echo(f"{report}")
+                return None
+            self.echo("Evaluating started...")
+            with torch.no_grad():
+                for ifold, (_, evalloader_fn) in enumerate(self.loader_list):
+                    report = self.infer(evalloader_fn()[1], samples=self.cfg.running.eval_samples)
+                    self.echo(f"{ifold:>2}th fold: {report}")
+            return None
+        report_by_fold = []
+        for ifold, (dataloader_fn, evalloader_fn) in enumerate(self.loader_list):
+            _, self.dataloader = dataloader_fn()
+            _, self.evalloader = evalloader_fn()
+            self.echo(f"Training started ({ifold})...")
+            self.last_time = 0.
+            self.total_loss = 0
+            self.total_step = 0
+            self.total_inst = 0
+            self.start_time = time.time()
+            self.report_by_epoch = []
+            for iepoch in range(int(self.cfg.optimizer.epochs)):
+                self.epoch(iepoch)
+            report_by_fold.append(self.report_by_epoch)
+            self.reinitialize(self.cfg, self.echo)
+        self.report_by_fold = report_by_fold
+        self.summary_report(report_by_fold)
+
+    # ------------------------------------------------------------------ esc50_clf.py:104-120
+    def summary_report(self, report):
+        report = np.array(report)
+        if report.ndim < 2 or report.shape[1] == 0:       # a rank other than 0 gets no report string: nothing to summarise
+            return
+        self.echo(f"\n{report}")
+        nfold, nepoch = report.shape[:2]
+        self.echo(f"Total {nepoch} epochs for each of {nfold} folds.")
+        report_sum = report.sum(0)
+        best_epoch = report_sum.argmax()
+        best_precisions = report[:, best_epoch]
+        mean, std = best_precisions.mean(), best_precisions.std()
+        self.echo(f"Best mean and std: {mean:2.2f} \\pm {std:2.2f} in the {best_epoch}th epoch.")
+        max_epoch = report.argmax(1)
+        max_precisions = report.max(1)
+        mean, std = max_precisions.mean(), max_precisions.std()
+        self.echo(f"Max mean and std: {mean:2.2f} \\pm {std:2.2f} in the {max_epoch}th epoch.")
+
+    # ------------------------------------------------------------------ esc50_clf.py:122-132
+    def make_batch(self, batch):
+        audios = torch.as_tensor(batch[0]).to(self.device, non_blocking=True).unsqueeze(1)
+        labels = torch.as_tensor(batch[1]).to(self.device, non_blocking=True)
+        return audios, labels, batch[2]
+
+    def step(self, audios, labels):
+        """zero_grad -> forward -> backward -> (replica gradient reduction) -> optimizer (esc50_clf.py:178-183).  Unlike the
+        contrastive heads' gradients, a classification head's are partial per rank (every rank scores its own rows, scaled by
+        1 / world): they join the SUM all-reduce with the other parameters outside the per-block buckets."""
+        from . import ops
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = self.model(audios, labels)
+        loss.backward(gradient=ops.unit_grad(loss.device) if loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32 else None)
+        if self.grad_sync is not None:
+            self.grad_sync.reduce_params([p for p in self.params if not getattr(p, "_vipant_bucketed", False)])
+            self.grad_sync.wait()
+        self.optimizer.step()
+        return loss
+
+    # ------------------------------------------------------------------ esc50_clf.py:150-238
+    def epoch(self, iepoch):
+        import re
+        all_time = defaultdict(list)
+        self.timeit(all_time)
+        nchunk = parallel.world_size()
+        ocfg = self.cfg.optimizer
+        warmup_step_rate = max(int(ocfg.warmup_steps) // 20, 1)
+        for step, batch in enumerate(self.dataloader, start=iepoch * len(self.dataloader)):
+            audios, labels, _ = self.make_batch(batch)
+            self.timeit(all_time, key="data")
+            if ocfg.use_lars:
+                adjust_learning_rate(ocfg, self.optimizer, self.dataloader, step)
+            warmup = (not ocfg.use_lars) and ocfg.warmup and self.total_step <= ocfg.warmup_steps
+            if warmup and (self.total_step % warmup_step_rate == 0 or self.total_step == 0):
+                ratio = self.total_step / ocfg.warmup_steps
+                for param_group in self.optimizer.param_groups:
+                    param_group["lr"] = ratio * param_group["initial_lr"]
+                lrs = " ".join(f"{g['lr']:.2e}" for g in self.optimizer.param_groups)
+                self.echo(f"warmup lr: {lrs} @ {self.total_step}")
+            loss = self.step(audios, labels)
+            if not ocfg.use_lars and ocfg.batch_sch and not warmup:
+                self.scheduler.step()
+            self.timeit(all_time, key="model")
+            self.total_step += 1
+            self.total_loss += loss.detach()
+            self.total_inst += audios.shape[0] * nchunk
+            if self.cfg.rank <= 0 and self.total_step % self.cfg.running.peep_rate == 0:
+                lr_w = self.optimizer.param_groups[0]["lr"]
+                lr_b = self.optimizer.param_groups[1]["lr"]
+                self.echo(
+                    f"epoch {iepoch:>4} step {self.total_step}\t"
+                    f"lr_w {lr_w:.2e} lr_b {lr_b:.2e} loss {float(self.total_loss) / self.total_step:.3f} "
+                    f"{self.total_inst / (time.time() - self.start_time):.2f} samples/s"
+                )
+            if self.total_step % self.cfg.running.save_rate == 0 or (
+                    self.cfg.running.save_epoch and self.total_step % len(self.dataloader) == 0):
+                report = ""
+                if self.evalloader is not None:
+                    self.model.train(False)
+                    with torch.no_grad():
+                        report = self.infer(self.evalloader, samples=self.cfg.running.eval_samples, iepoch=iepoch)
+                    self.model.train(True)
+                if report != "":
+                    precision = re.search(r"=\s(\d+\.\d+)\s\@", report)
+                    assert precision is not None, f"invalid report: `{report}`"
+                    self.report_by_epoch.append(float(precision.group(1)))
+                    self.echo(f"{report}")
+            self.timeit(all_time, key="report")
+        if not ocfg.use_lars and not ocfg.batch_sch:
+            self.scheduler.step()
+        self.timeit(all_time, show=True)
+
+    # ------------------------------------------------------------------ esc50_clf.py:240-258
+    def infer(self, dataloader, samples=float("inf"), iepoch=0, gold_file=None):
+        nsample = 0
+        start_time = time.time()
+        for ibatch, batch in enumerate(dataloader):
+            if nsample >= samples:
+                break
+            audios, labels, names = self.make_batch(batch)
+            self.model(audios, labels, names=names)
+            nsample += audios.shape[0]
+        self.echo(f"# sample {nsample}; {nsample / (time.time() - start_time):.2f} samples/s")
+        return self.model.report()
+
+    # ------------------------------------------------------------------ esc50_clf.py:294-325
+    def standard_zero_shot(self, samples=float("inf"), iepoch=0):
+        import re
+        text_features = self.model.encode_text(torch.tensor(self.lid2int, device=self.device))
+        for ifold, (_, evalloader_fn) in enumerate(self.loader_list):
+            _, dataloader = evalloader_fn()
+            nsample = 0
+            start_time = time.time()
+            for ibatch, batch in enumerate(dataloader):
+                if nsample >= samples:
+                    break
+                audios, labels, names = self.make_batch(batch)
+                self.model(audios, labels, names=names)
+                nsample += audios.shape[0]
+            self.echo(f"{ifold:>2}th fold: # sample {nsample}; {nsample / (time.time() - start_time):.2f} samples/s")
+        report = self.model.report(text=text_features, label_map=self.label_map)
+        self.echo(f"{report}")
+        precision = re.search(r"=\s(\d+\.\d+)\s\@", report)
+        assert precision is not None, f"invalid report: `{report}`"
+        return f"{float(precision.group(1)):2.2f} for zero-shot classification."
+
+
+__all__ = ["Monitor", "VAMonitor", "VALMonitor", "ESCMonitor", "SyntheticLoader", "SyntheticFolds"]

@@ -1387,3 +1387,180 @@ class BarlowFn(torch.autograd.Function):
         grads.append(dW[L])
         grads = [g if need[3 + k] else None for k, g in enumerate(grads)]
         return (dxs[0], dxs[1], None, *grads)
+
+
+# ---------------------------------------------------------------------------------- classification heads
+def _ls_scalar(logit_scale: Optional[torch.Tensor], device):
+    return None if logit_scale is None else logit_scale.detach().reshape(1).to(device=device, dtype=F32)
+
+
+def softmax_ce(z: torch.Tensor, labels: torch.Tensor, logit_scale: torch.Tensor, *, C: Optional[int] = None, row0: int = 0,
+               nrows: Optional[int] = None, grad_scale: float = 1.0, want_grad: bool = True, ldd: Optional[int] = None,
+               want_pred: bool = True):
+    """nn.CrossEntropyLoss()(exp(logit_scale) * z[:, :C], labels) over rows [row0, row0 + nrows) of the un-scaled fp32 logits
+    z [B, ldz] -> (loss fp32 [1], dz bf16 [B, ldd] | None, dscale fp32 [1] | None, pred int32 [B] | None).  The loss is the
+    scored rows' share of the batch mean (denominator B); rows outside the range are not written in dz / pred."""
+    _need(z, F32, "softmax_ce.z"); _need(labels, I64, "softmax_ce.labels")
+    B = z.shape[0]
+    C = z.shape[1] if C is None else int(C)
+    nrows = B - row0 if nrows is None else int(nrows)
+    ldd = (z.shape[1] if ldd is None else int(ldd))
+    dev = z.device
+    loss = torch.empty((1,), dtype=F32, device=dev)
+    dz = torch.empty((B, ldd), dtype=BF16, device=dev) if want_grad else None
+    dscale = torch.empty((1,), dtype=F32, device=dev) if want_grad else None
+    pred = torch.empty((B,), dtype=torch.int32, device=dev) if want_pred else None
+    ws = scratch("classify", query("vipant_softmax_ce_workspace_bytes", nrows), dev)
+    call("vipant_softmax_ce", z.data_ptr(), z.stride(0), labels.data_ptr(), _ls_scalar(logit_scale, dev).data_ptr(), loss.data_ptr(),
+         _ptr(dz), ldd, _ptr(dscale), _ptr(pred), int(row0), nrows, float(grad_scale), B, C, ws.data_ptr(), ws.numel(), _stream())
+    return loss, dz, dscale, pred
+
+
+def bce_logits(z: torch.Tensor, targets: torch.Tensor, logit_scale: Optional[torch.Tensor], *, C: Optional[int] = None,
+               row0: int = 0, nrows: Optional[int] = None, grad_scale: float = 1.0, want_grad: bool = True,
+               ldd: Optional[int] = None, want_prob: bool = False):
+    """nn.BCEWithLogitsLoss()(exp(logit_scale) * z[:, :C], targets) (logit_scale None: scale 1) -> (loss fp32 [1], dz bf16
+    [B, ldd] | None, dscale fp32 [1] | None, prob fp32 [B, C] | None = sigmoid of the scaled logits).  targets uint8 [B, C]."""
+    _need(z, F32, "bce_logits.z"); _need(targets, torch.uint8, "bce_logits.targets")
+    B = z.shape[0]
+    C = z.shape[1] if C is None else int(C)
+    assert targets.shape[0] == B and targets.shape[1] >= C, (z.shape, targets.shape)
+    nrows = B - row0 if nrows is None else int(nrows)
+    ldd = (z.shape[1] if ldd is None else int(ldd))
+    dev = z.device
+    ls = _ls_scalar(logit_scale, dev)
+    loss = torch.empty((1,), dtype=F32, device=dev)
+    dz = torch.empty((B, ldd), dtype=BF16, device=dev) if want_grad else None
+    dscale = torch.empty((1,), dtype=F32, device=dev) if (want_grad and ls is not None) else None
+    prob = torch.empty((B, C), dtype=F32, device=dev) if want_prob else None
+    ws = scratch("classify", query("vipant_bce_logits_workspace_bytes", nrows), dev)
+    call("vipant_bce_logits", z.data_ptr(), z.stride(0), targets.data_ptr(), targets.stride(0), _ptr(ls), loss.data_ptr(), _ptr(dz),
+         ldd, _ptr(dscale), _ptr(prob), C, int(row0), nrows, float(grad_scale), B, C, ws.data_ptr(), ws.numel(), _stream())
+    return loss, dz, dscale, prob
+
+
+_padded: Dict[tuple, tuple] = {}
+
+
+def padded_classifier(w: torch.Tensor, bias: Optional[torch.Tensor], Cp: int):
+    """The last Linear of a classification head with its class dimension padded to Cp rows: (bf16 [Cp, K], its transpose bf16
+    [K, Cp], fp32 bias [Cp] | None), rows / entries C .. Cp-1 zero.  vipant_gemm_nt needs N % 4 == 0 and K % 64 == 0 and the
+    input-gradient contraction has the classes as K.  The fp32 staging copies persist per weight (their pad stays zero) and are
+    refreshed, with one cast launch, when the parameter's version changes."""
+    key = (w.data_ptr(), tuple(w.shape), Cp, None if bias is None else bias.data_ptr())
+    ver = (w._version, None if bias is None else bias._version)
+    hit = _padded.get(key)
+    if hit is None:
+        while len(_padded) >= 64:
+            _padded.pop(next(iter(_padded)))
+        hit = _padded[key] = dict(w32=torch.zeros((Cp, w.shape[1]), dtype=F32, device=w.device),
+                                  b32=None if bias is None else torch.zeros((Cp,), dtype=F32, device=w.device),
+                                  ver=None, keep=(w.untyped_storage(), None if bias is None else bias.untyped_storage()))
+    if hit["ver"] != ver:
+        C = w.shape[0]
+        hit["w32"][:C].copy_(w.detach())
+        if bias is not None:
+            hit["b32"][:C].copy_(bias.detach())
+        hit["wb"], hit["wt"] = cast_bf16(hit["w32"], transpose=True)
+        hit["ver"] = ver
+    return hit["wb"], hit["wt"], hit["b32"]
+
+
+class ClassifierMeta:
+    """What ClassifierFn needs besides its differentiable inputs: the loss ("ce": int64 labels [B]; "bce": uint8 multi-hot
+    targets [B, C]), the class count, 1 / world for a replica's share of the gradient, and what the eval path wants back.
+    `pred` / `prob` receive the arg-max columns / sigmoid scores of the last forward."""
+
+    def __init__(self, kind: str, nclass: int, grad_scale: float = 1.0, want_pred: bool = False, want_prob: bool = False):
+        assert kind in ("ce", "bce"), kind
+        self.kind, self.nclass, self.grad_scale = kind, int(nclass), float(grad_scale)
+        self.want_pred, self.want_prob = bool(want_pred), bool(want_prob)
+        self.pred = self.prob = None
+
+
+class ClassifierFn(torch.autograd.Function):
+    """ClassificationHead.forward / BCELossHead.forward (cvap/module/decoder/loss_head.py:409-419, loss_more.py:133-143) as ONE
+    autograd node: [LayerNorm -> Linear] x (L + 1), the temperature and the loss.
+
+    x fp32 [B, E]; target: labels or multi-hot targets (see ClassifierMeta); logit_scale: the log temperature (a parameter, a
+    plain tensor, or None for scale 1); params = (ln_w_0, ln_b_0, W_0, b_0, ..., ln_w_L, ln_b_L, W_L, b_L | None).  The last
+    Linear runs with its class dimension padded to a multiple of 64 (padded_classifier); the loss kernel reads the C valid
+    columns and writes dz with zero pad columns, so the pad never enters the loss or a gradient.  LayerNorm, the contractions,
+    the bias sums (from the weight-gradient contraction's operand tiles and the LayerNorm backward's `dx_colsum`) are the
+    library's; forward and loss gradient are one pass (vipant_softmax_ce / vipant_bce_logits), the backward is contractions."""
+
+    @staticmethod
+    def forward(ctx, x, target, logit_scale, meta, *params):
+        _need(x, F32, "classifier.x")
+        x = x.contiguous()
+        L = len(params) // 4 - 1
+        dev, B, C = x.device, x.shape[0], meta.nclass
+        Cp = (C + 63) // 64 * 64
+        need = ctx.needs_input_grad
+        want = any(need)
+        h, saved = x, []
+        for i in range(L + 1):
+            g, b, W, bias = params[4 * i:4 * i + 4]
+            y, _, mean, rstd = layernorm_fwd(h, g, b)
+            saved.append((h, y, mean, rstd))
+            if i < L:
+                h = gemm_nt(y, cached_bf16(W), torch.empty((B, W.shape[0]), dtype=F32, device=dev), bias=bias, epi=EPI_F32)
+            else:
+                wb, wt, b32 = padded_classifier(W, bias, Cp)
+                z = gemm_nt(y, wb, torch.empty((B, Cp), dtype=F32, device=dev), bias=b32, epi=EPI_F32)
+        if meta.kind == "ce":
+            loss, dz, dls, pred = softmax_ce(z, target, logit_scale, C=C, grad_scale=meta.grad_scale, want_grad=want,
+                                             want_pred=meta.want_pred)
+            meta.pred = pred
+        else:
+            loss, dz, dls, prob = bce_logits(z, target, logit_scale, C=C, grad_scale=meta.grad_scale, want_grad=want,
+                                             want_prob=meta.want_prob)
+            meta.prob = prob
+        if want:
+            ctx.saved, ctx.dz, ctx.dls, ctx.wt, ctx.params = saved, dz, dls, wt, params
+            ctx.shapes = (L, C, Cp, None if logit_scale is None else tuple(logit_scale.shape))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        L, C, Cp, ls_shape = ctx.shapes
+        saved, params, need = ctx.saved, ctx.params, ctx.needs_input_grad
+        dev = ctx.dz.device
+        B = ctx.dz.shape[0]
+        grads = [None] * len(params)
+        dy_b, dx = ctx.dz, None                       # bf16 gradient of layer i's Linear output
+        for i in range(L, -1, -1):
+            g, b, W, bias = params[4 * i:4 * i + 4]
+            h, y, mean, rstd = saved[i]
+            K = W.shape[1]
+            rows = Cp if i == L else W.shape[0]
+            dW = torch.empty((rows, K), dtype=F32, device=dev)
+            db = torch.empty((rows,), dtype=F32, device=dev) if (i == L and bias is not None) else None
+            gemm_tn(dy_b, y, dW, a_colsum=db)                         # hidden layers' bias sums came from the LayerNorm backward
+            grads[4 * i + 2] = dW[:W.shape[0]]
+            if db is not None:
+                grads[4 * i + 3] = db[:W.shape[0]]
+            wt = ctx.wt if i == L else cached_bf16(W, transpose_only=True)
+            dyl = gemm_nt(dy_b, wt, torch.empty((B, K), dtype=F32, device=dev), epi=EPI_F32)
+            dg, dbeta = torch.empty_like(g), torch.empty_like(b)
+            if i > 0:
+                dy_b = torch.empty((B, K), dtype=BF16, device=dev)
+                dbias = torch.empty((K,), dtype=F32, device=dev)      # = d bias of Linear i - 1 (column sums of its output gradient)
+                layernorm_bwd(dyl, h, mean, rstd, g, dx_bf16=dy_b, dgamma=dg, dbeta=dbeta, dx_colsum=dbias)
+                grads[4 * (i - 1) + 3] = dbias
+            elif need[0]:
+                dx = torch.empty((B, K), dtype=F32, device=dev)
+                layernorm_bwd(dyl, h, mean, rstd, g, dx=dx, dgamma=dg, dbeta=dbeta)
+            else:
+                layernorm_bwd(dyl, h, mean, rstd, g, dx_bf16=torch.empty((B, K), dtype=BF16, device=dev), dgamma=dg, dbeta=dbeta)
+            grads[4 * i], grads[4 * i + 1] = dg, dbeta
+        dls = ctx.dls
+        ctx.saved = ctx.dz = ctx.params = ctx.wt = None
+        unit = dloss.dim() == 0 and dloss.data_ptr() == unit_grad(dloss.device).data_ptr()
+        if not unit:                                   # an upstream factor other than the trainer's cached 1.0
+            dx = None if dx is None else dx * dloss
+            grads = [None if t is None else t * dloss for t in grads]
+            dls = None if dls is None else dls * dloss
+        grads = [t if (t is not None and need[4 + k]) else None for k, t in enumerate(grads)]
+        dls = dls.reshape(ls_shape) if (dls is not None and need[2] and ls_shape is not None) else None
+        return (dx, None, dls, None, *grads)
