@@ -85,20 +85,25 @@ int32_t vipant_colsum_bf16(const uint16_t* X, int64_t ldx, float* out, int64_t M
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- LayerNorm (clip/model.py:154-160: fp32 statistics, eps 1e-5) -----------------------------------
- * x fp32 rows (row stride ldx elements) -> y bf16 [M, D] (optional); mean / rstd fp32 [M] saved for backward.
- * y_f32 (optional, may be NULL) receives the fp32 result as well (ln_pre writes the residual stream).
+ * x rows (fp32, or fp16 with VIPANT_STREAM_IN_F16 in `stream_flags`, below; row stride ldx elements) -> y bf16 [M, D] (optional);
+ * mean / rstd fp32 [M] saved for backward.  y_f32 (optional, may be NULL) receives the fp32 result as well (ln_pre writes the
+ * residual stream).
  * add (optional bf16 [M, D]): the residual add `x + branch` of ResidualAttentionBlock.forward (cvap/module/val.py:520-521)
- * fused in front of the norm; sum_out (optional fp32 [M, D]) receives x + add (the new residual stream). */
-int32_t vipant_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta, uint16_t* y,
-                             float* y_f32, float* mean, float* rstd, int64_t M, int64_t D, const uint16_t* add,
-                             float* sum_out, void* stream);
+ * fused in front of the norm; sum_out (optional [M, D], fp32 or -- VIPANT_STREAM_OUT_F16 -- fp16) receives x + add (the new
+ * residual stream).
+ * q / qscale (optional, both or neither; here and in vipant_layernorm_bwd): the block quantisation of the bf16 output fused into the
+ * pass (the row is in registers anyway): q bytes [M, D] / qscale bytes [vipant_mx_scale_bytes(M, D)] = vipant_quant_e4m3_mx of y
+ * resp. dx_bf16, bit for bit. */
+int32_t vipant_layernorm_fwd(const void* x, int64_t ldx, const float* gamma, const float* beta, uint16_t* y, float* y_f32,
+                             float* mean, float* rstd, int64_t M, int64_t D, const uint16_t* add, void* sum_out, uint8_t* q,
+                             uint8_t* qscale, int32_t stream_flags, void* stream);
 /* Precision of the residual stream INSIDE the transformer stack (`stream_flags` of the operators below): fp32, or fp16 -- the
  * reference's own autocast precision (clip/model.py:157-160 casts the fp32 LayerNorm result back to the fp16 stream) -- with fp32
  * statistics and the norm taken on the unrounded sum.  IN: the `x` argument is fp16; OUT: the `x_out` / `sum_out` argument is. */
 #define VIPANT_STREAM_IN_F16 1
 #define VIPANT_STREAM_OUT_F16 2
-#define VIPANT_STREAM_FEW_ROWS 0x100 /* (vipant_ln_mlp_quickgelu_bwd_e4m3) its contractions are VIPANT_EPI_FEW_ROWS launches */
-#define VIPANT_STREAM_ACT_Q 0x200 /* (vipant_ln_qkv_bwd_e4m3) the plan's activation scratch already holds dqkv's e4m3 form (vipant_mha_bwd_e4m3) */
+#define VIPANT_STREAM_FEW_ROWS 0x100 /* (vipant_ln_mlp_quickgelu_bwd) its contractions are VIPANT_EPI_FEW_ROWS launches */
+#define VIPANT_STREAM_ACT_Q 0x200 /* (vipant_ln_qkv_bwd) the plan's activation scratch already holds dqkv's e4m3 form (vipant_mha_bwd) */
 /* out fp32 [M, D] = x (fp32, or fp16 with VIPANT_STREAM_IN_F16) + add bf16 (the last block's residual add, no norm behind it). */
 int32_t vipant_residual_add(const void* x, const uint16_t* add, float* out, int64_t n, int32_t stream_flags, void* stream);
 /* dx[M,D] = dres (optional residual-stream gradient) + LN'(dy); outputs dx_f32 (optional) and dx_bf16 (optional).
@@ -113,17 +118,25 @@ size_t vipant_layernorm_bwd_workspace_bytes(int64_t M, int64_t D);
 int32_t vipant_layernorm_bwd(const void* dy, int32_t flags, const void* x, int64_t ldx, const float* mean,
                              const float* rstd, const float* gamma, const void* dres, float* dx_f32, int64_t lddx,
                              uint16_t* dx_bf16, float* dgamma, float* dbeta, float* dx_colsum, int32_t accumulate,
-                             int64_t M, int64_t D, void* workspace, size_t workspace_bytes, void* stream);
+                             int64_t M, int64_t D, void* workspace, size_t workspace_bytes, uint8_t* q, uint8_t* qscale,
+                             void* stream);
 
 /* ---- multi-head attention core (nn.MultiheadAttention inside ResidualAttentionBlock,
  *      cvap/module/val.py:511-517): softmax(q k^T / sqrt(64) [+ causal mask]) v, head dim 64 -----------
  * qkv bf16 [batch*S, 3*D] packed q|k|v (in_proj row order), out bf16 [batch*S, D]; lse fp32 [batch, H, S]
- * (natural-log row log-sum-exp of the scaled scores, saved for backward). */
-int32_t vipant_mha_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int64_t batch, int64_t S, int64_t H,
-                       int32_t causal, void* stream);
+ * (natural-log row log-sum-exp of the scaled scores, saved for backward).
+ * out_q / out_scale and dqkv_q / dqkv_scale (optional, both or neither; H even, i.e. D % 128 == 0): the call also leaves the e4m3 +
+ * block-scale form of its result for the contraction that follows (out_proj; in_proj^T): `out` [M, D] and the dQ columns of `dqkv`
+ * [M, 3 D] -- made by a pass behind the kernel -- in the block-uniform form (vipant_quant_e4m3_mx32, bit for bit; round 6), the
+ * dK | dV columns the streamed backward emits from its own epilogue in the row-wise form (vipant_quant_e4m3_mx, bit for bit):
+ * vipant_mx_uniform32_cols makes those uniform too where a weight gradient wants them.  The streamed single-pass backward
+ * (224 < S <= 320, no mask) emits the dK | dV columns from its own epilogue; everything else -- dQ, the other backward shapes, the
+ * forward -- is the stand-alone pass enqueued behind the kernel.  No reference counterpart (BASELINE.json configs[4]). */
+int32_t vipant_mha_fwd(const uint16_t* qkv, uint16_t* out, float* lse, uint8_t* out_q, uint8_t* out_scale, int64_t batch, int64_t S,
+                       int64_t H, int32_t causal, void* stream);
 /* dqkv bf16 [batch*S, 3*D] from dout bf16 [batch*S, D]; delta fp32 [batch, H, S] is scratch. */
-int32_t vipant_mha_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
-                       float* delta, uint16_t* dqkv, int64_t batch, int64_t S, int64_t H, int32_t causal,
+int32_t vipant_mha_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
+                       uint16_t* dqkv, uint8_t* dqkv_q, uint8_t* dqkv_scale, int64_t batch, int64_t S, int64_t H, int32_t causal,
                        void* stream);
 
 /* The patch embedding written straight into the token matrix (ViTPreEncoder, cvap/module/val.py:249-257): for m = item * P + patch,
@@ -240,18 +253,6 @@ size_t vipant_gemm_tn_e4m3_workspace_bytes(int64_t M, int64_t P, int64_t Q);
 int32_t vipant_gemm_tn_e4m3(const uint8_t* A, int64_t lda, const uint8_t* sa, const uint8_t* B, int64_t ldb, const uint8_t* sb, float* C,
                             int64_t ldc, int64_t M, int64_t P, int64_t Q, int32_t accumulate, float* a_colsum, void* workspace,
                             size_t workspace_bytes, void* stream);
-/* vipant_mha_fwd / vipant_mha_bwd that also leave the e4m3 + block-scale form of their result for the contraction that follows
- * (out_proj; in_proj^T): `out` [M, D] and the dQ columns of `dqkv` [M, 3 D] -- made by a pass behind the kernel -- in the block-uniform
- * form (vipant_quant_e4m3_mx32, bit for bit; round 6), the dK | dV columns the streamed backward emits from its own epilogue in the
- * row-wise form (vipant_quant_e4m3_mx, bit for bit): vipant_mx_uniform32_cols makes those uniform too where a weight gradient wants them.  No reference counterpart
- * (BASELINE.json configs[4]).  The streamed single-pass backward (224 < S <= 320, no mask) emits the dK | dV columns from its own
- * epilogue; everything else -- dQ, the other backward shapes, the forward -- is the stand-alone pass enqueued behind the kernel.
- * H even (D % 128 == 0). */
-int32_t vipant_mha_fwd_e4m3(const uint16_t* qkv, uint16_t* out, float* lse, uint8_t* out_q, uint8_t* out_scale, int64_t batch,
-                            int64_t S, int64_t H, int32_t causal, void* stream);
-int32_t vipant_mha_bwd_e4m3(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                            uint16_t* dqkv, uint8_t* dqkv_q, uint8_t* dqkv_scale, int64_t batch, int64_t S, int64_t H,
-                            int32_t causal, void* stream);
 /* C[M, N] (bf16) = dequant(A, sa) dequant(B, sb)^T (+ bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (fp32 accumulation; the scales ride
  * the instruction's block-scale operands).  A [M, K] e4m3: an activation, sa = its BLOCK scales (vipant_quant_e4m3_mx layout); B [N, K]
  * e4m3: a weight matrix, sb = one scale per row (vipant_quant_e4m3_rows).  Epilogues: VIPANT_EPI_BF16, VIPANT_EPI_QUICKGELU_D8,
@@ -270,10 +271,8 @@ int32_t vipant_conv_weight_prep(const float* w, uint16_t* out, int64_t O, int64_
  * patch (i, j) at (i*sh, j*sw), row order t-major (token = i*ncol + j). */
 int32_t vipant_im2col(const float* x, uint16_t* out, int64_t b, int64_t C, int64_t T, int64_t F, int64_t ph,
                       int64_t pw, int64_t sh, int64_t sw, void* stream);
-/* tokens[b, 0, :] = cls + pos[0]; tokens[b, 1+p, :] = patches[b*P + p, :] + pos[1+p]  (val.py:253-257). fp32. */
-int32_t vipant_assemble_tokens(const float* patches, const float* cls, const float* pos, float* tokens, int64_t b,
-                               int64_t P, int64_t D, void* stream);
-/* backward of assemble_tokens: dpatches bf16 [b*P, D], dcls [D] and dpos [S, D] fp32 (+)=. */
+/* backward of the token assembly tokens[b, 0, :] = cls + pos[0]; tokens[b, 1+p, :] = patches[b*P + p, :] + pos[1+p] (val.py:253-257;
+ * the forward is vipant_gemm_nt_tokens + vipant_tokens_cls_rows): dpatches bf16 [b*P, D], dcls [D] and dpos [S, D] fp32 (+)=. */
 int32_t vipant_assemble_tokens_bwd(const float* dtokens, uint16_t* dpatches, float* dcls, float* dpos,
                                    int32_t accumulate, int64_t b, int64_t P, int64_t D, void* stream);
 /* effective-kernel gradient [O, khw] fp32 -> conv1.weight.grad [O, Cin, khw] (+)= g / Cin per channel. */
@@ -413,54 +412,13 @@ int32_t vipant_bce_logits(const float* z, int64_t ldz, const uint8_t* targets, i
  * `workspace` of the backward entry points: vipant_block_workspace_bytes(M, D) bytes, 256-byte aligned. */
 size_t vipant_block_workspace_bytes(int64_t M, int64_t D);
 
-/* K2 -- ln_1 + packed in_proj of nn.MultiheadAttention (cvap/module/val.py:519-520, 500; clip/model.py:154-160).
- * h bf16 [M,D] = LN(x (+ add)), mean / rstd fp32 [M], qkv bf16 [M,3D] = h . w_qkv^T + b_qkv. */
-int32_t vipant_ln_qkv_fwd(const float* x, const uint16_t* add, float* x_out, const float* gamma, const float* beta,
-                          const uint16_t* w_qkv, const float* b_qkv, uint16_t* h, float* mean, float* rstd, uint16_t* qkv,
-                          int64_t M, int64_t D, void* stream);
-/* dstream fp32 [M,D]: in = gradient of the residual stream after this block's attention branch, out = gradient before the block
- * (in place); dx_bf16 its bf16 copy.  dstream == NULL: the gradient stream is kept in bf16 only -- dx_bf16 is read as the incoming
- * gradient and overwritten with the outgoing one (the forward stream stays fp32; profiles/r2_stream_precision.md, model D).
- * dh bf16 [M,D] scratch; dw fp32 [3D,D], db fp32 [3D], dgamma / dbeta fp32 [D];
- * dx_colsum (optional fp32 [D]) = column sums of the produced gradient (= d c_proj.bias of the block below). */
-int32_t vipant_ln_qkv_bwd(const uint16_t* dqkv, const uint16_t* w_qkv_t, const uint16_t* h, const float* x, const float* mean,
-                          const float* rstd, const float* gamma, float* dstream, uint16_t* dx_bf16, uint16_t* dh, float* dw,
-                          float* db, float* dgamma, float* dbeta, float* dx_colsum, int64_t M, int64_t D, void* workspace,
-                          size_t workspace_bytes, void* stream);
-
-/* K4 -- out_proj (cvap/module/val.py:517, 520).  residual == NULL: out bf16 [M,N] = a . w^T + bias (the step's form: the add
- * happens in the next LayerNorm pass); residual fp32 [M,N]: out fp32 [M,N] = a . w^T + bias + residual (stand-alone form). */
-int32_t vipant_gemm_bias_residual_fwd(const uint16_t* a, const uint16_t* w, const float* bias, const float* residual, void* out,
-                                      int64_t M, int64_t N, int64_t K, void* stream);
-/* da bf16 [M,K] = dy . w (w_t = w^T, [K,N]); dw fp32 [N,K] = dy^T a.  (d bias = column sums of dy: see dx_colsum above.) */
-int32_t vipant_gemm_bias_residual_bwd(const uint16_t* dy, const uint16_t* w_t, const uint16_t* a, uint16_t* da, float* dw,
-                                      int64_t M, int64_t N, int64_t K, void* workspace, size_t workspace_bytes, void* stream);
-
-/* K5 -- ln_2 + c_fc + QuickGELU + c_proj (cvap/module/val.py:502-506, 521; clip/model.py:163-165).
- * h bf16 [M,D] = LN(x (+ add)); u = h . w_fc^T + b_fc; g bf16 [M,4D] = u * sigmoid(1.702 u); dcode uint8 [M,4D] = 8-bit code of
- * QuickGELU'(u) (all the backward needs of u: VIPANT_EPI_QUICKGELU_D8); y bf16 [M,D] = g . w_proj^T + b_proj. */
-int32_t vipant_ln_mlp_quickgelu_fwd(const float* x, const uint16_t* add, float* x_out, const float* gamma, const float* beta,
-                                    const uint16_t* w_fc, const float* b_fc, const uint16_t* w_proj, const float* b_proj,
-                                    uint16_t* h, float* mean, float* rstd, uint8_t* dcode, uint16_t* g, uint16_t* y, int64_t M,
-                                    int64_t D, void* stream);
-/* dcode, g again from the saved h (activation-memory plan `running.recompute_mlp`). */
-int32_t vipant_mlp_quickgelu_recompute(const uint16_t* h, const uint16_t* w_fc, const float* b_fc, uint8_t* dcode, uint16_t* g,
-                                       int64_t M, int64_t D, void* stream);
-/* dy bf16 [M,D] = gradient of the MLP branch output (= bf16 copy of the stream gradient); dstream as in vipant_ln_qkv_bwd;
- * du bf16 [M,4D], dh bf16 [M,D] scratch; dw_proj fp32 [D,4D], dw_fc fp32 [4D,D], db_fc fp32 [4D];
- * dx_colsum (optional fp32 [D]) = d out_proj.bias. */
-int32_t vipant_ln_mlp_quickgelu_bwd(const uint16_t* dy, const uint16_t* w_proj_t, const uint16_t* w_fc_t, const uint8_t* dcode,
-                                    const uint16_t* g, const uint16_t* h, const float* x, const float* mean, const float* rstd,
-                                    const float* gamma, float* dstream, uint16_t* dx_bf16, uint16_t* du, uint16_t* dh,
-                                    float* dw_proj, float* dw_fc, float* db_fc, float* dgamma, float* dbeta, float* dx_colsum,
-                                    int64_t M, int64_t D, void* workspace, size_t workspace_bytes, void* stream);
-
-/* ---- The same block operators with e4m3 operands in their NT contractions (BASELINE.json configs[4], "fp8 MFMA weights") ----
- * `plan` carries the pre-quantised weights (vipant_quant_e4m3_rows of the SAME matrices, in the SAME orientation, as the bf16
- * weight arguments, which are then unused and may be NULL) and the scratch the operator quantises its activation into; every NT
- * contraction becomes vipant_gemm_nt_e4m3 on an activation block-quantised by its producer (a LayerNorm pass, the epilogue of the
- * contraction before it) or, for the two attention outputs, by vipant_quant_e4m3_mx.  The weight-gradient contractions, LayerNorm, the
- * attention core and the residual stream are unchanged (bf16 / fp32).  plan == NULL: exactly the bf16 operator.
+/* The `plan` argument of the block operators: e4m3 operands in their NT contractions (BASELINE.json configs[4], "fp8 MFMA weights").
+ * plan == NULL: the bf16 operator.  Otherwise `plan` carries the pre-quantised weights (vipant_quant_e4m3_rows of the SAME matrices,
+ * in the SAME orientation, as the bf16 weight arguments, which are then unused and may be NULL) and the scratch the operator
+ * quantises its activation into; every NT contraction becomes vipant_gemm_nt_e4m3 on an activation block-quantised by its producer
+ * (a LayerNorm pass, the epilogue of the contraction before it) or, for the two attention outputs, by vipant_mha_fwd / vipant_mha_bwd.
+ * The weight-gradient contractions (unless tn_e4m3, below), LayerNorm, the attention core and the residual stream are unchanged
+ * (bf16 / fp32).
  * w_q / w_scale: the operator's (first) weight; w2_q / w2_scale: the second weight of the MLP operators (forward: w_fc then w_proj;
  * backward: w_proj_t then w_fc_t), one scale per row; act_q: bytes [M, 4D] (the widest activation); act_scale: its block scales, one
  * per 32 elements of a row in the MX layout of vipant_quant_e4m3_mx, vipant_mx_scale_bytes(M, 4D) bytes. */
@@ -493,47 +451,59 @@ typedef struct vipant_fp8_plan {
     const uint8_t* keep2_q;
     const uint8_t* keep2_scale;
 } vipant_fp8_plan;
-/* LayerNorm with the block quantisation of its bf16 output fused (the row is in registers anyway): q bytes [M, D] / qscale bytes
- * [vipant_mx_scale_bytes(M, D)] = vipant_quant_e4m3_mx of y resp. dx_bf16, bit for bit; both NULL: exactly vipant_layernorm_fwd /
- * vipant_layernorm_bwd. */
-int32_t vipant_layernorm_fwd_e4m3(const void* x, int64_t ldx, const float* gamma, const float* beta, uint16_t* y, float* y_f32,
-                                  float* mean, float* rstd, int64_t M, int64_t D, const uint16_t* add, void* sum_out, uint8_t* q,
-                                  uint8_t* qscale, int32_t stream_flags, void* stream);
-int32_t vipant_layernorm_bwd_e4m3(const void* dy, int32_t flags, const void* x, int64_t ldx, const float* mean, const float* rstd,
-                                  const float* gamma, const void* dres, float* dx_f32, int64_t lddx, uint16_t* dx_bf16,
-                                  float* dgamma, float* dbeta, float* dx_colsum, int32_t accumulate, int64_t M, int64_t D,
-                                  void* workspace, size_t workspace_bytes, uint8_t* q, uint8_t* qscale, void* stream);
-int32_t vipant_ln_qkv_fwd_e4m3(const void* x, const uint16_t* add, void* x_out, const float* gamma, const float* beta,
-                               const uint16_t* w_qkv, const float* b_qkv, uint16_t* h, float* mean, float* rstd, uint16_t* qkv,
-                               int64_t M, int64_t D, const vipant_fp8_plan* plan, int32_t stream_flags, void* stream);
-int32_t vipant_ln_qkv_bwd_e4m3(const uint16_t* dqkv, const uint16_t* w_qkv_t, const uint16_t* h, const void* x, const float* mean,
-                               const float* rstd, const float* gamma, float* dstream, uint16_t* dx_bf16, uint16_t* dh, float* dw,
-                               float* db, float* dgamma, float* dbeta, float* dx_colsum, int64_t M, int64_t D, void* workspace,
-                               size_t workspace_bytes, const vipant_fp8_plan* plan, int32_t stream_flags, void* stream);
-int32_t vipant_gemm_bias_residual_fwd_e4m3(const uint16_t* a, const uint16_t* w, const float* bias, const float* residual, void* out,
-                                           int64_t M, int64_t N, int64_t K, const vipant_fp8_plan* plan, void* stream);
-int32_t vipant_gemm_bias_residual_bwd_e4m3(const uint16_t* dy, const uint16_t* w_t, const uint16_t* a, uint16_t* da, float* dw,
-                                           int64_t M, int64_t N, int64_t K, void* workspace, size_t workspace_bytes,
-                                           const vipant_fp8_plan* plan, void* stream);
-int32_t vipant_ln_mlp_quickgelu_fwd_e4m3(const void* x, const uint16_t* add, void* x_out, const float* gamma, const float* beta,
-                                         const uint16_t* w_fc, const float* b_fc, const uint16_t* w_proj, const float* b_proj,
-                                         uint16_t* h, float* mean, float* rstd, uint8_t* dcode, uint16_t* g, uint16_t* y, int64_t M,
-                                         int64_t D, const vipant_fp8_plan* plan, int32_t stream_flags, void* stream);
-int32_t vipant_mlp_quickgelu_recompute_e4m3(const uint16_t* h, const uint16_t* w_fc, const float* b_fc, uint8_t* dcode, uint16_t* g,
-                                            int64_t M, int64_t D, const vipant_fp8_plan* plan, void* stream);
-int32_t vipant_ln_mlp_quickgelu_bwd_e4m3(const uint16_t* dy, const uint16_t* w_proj_t, const uint16_t* w_fc_t, const uint8_t* dcode,
-                                         const uint16_t* g, const uint16_t* h, const void* x, const float* mean, const float* rstd,
-                                         const float* gamma, float* dstream, uint16_t* dx_bf16, uint16_t* du, uint16_t* dh,
-                                         float* dw_proj, float* dw_fc, float* db_fc, float* dgamma, float* dbeta, float* dx_colsum,
-                                         int64_t M, int64_t D, void* workspace, size_t workspace_bytes, const vipant_fp8_plan* plan,
-                                         int32_t stream_flags, void* stream);
+
+/* K2 -- ln_1 + packed in_proj of nn.MultiheadAttention (cvap/module/val.py:519-520, 500; clip/model.py:154-160).
+ * h bf16 [M,D] = LN(x (+ add)), mean / rstd fp32 [M], qkv bf16 [M,3D] = h . w_qkv^T + b_qkv.  x / x_out: fp32, or fp16 as
+ * `stream_flags` (VIPANT_STREAM_*) says. */
+int32_t vipant_ln_qkv_fwd(const void* x, const uint16_t* add, void* x_out, const float* gamma, const float* beta,
+                          const uint16_t* w_qkv, const float* b_qkv, uint16_t* h, float* mean, float* rstd, uint16_t* qkv,
+                          int64_t M, int64_t D, const vipant_fp8_plan* plan, int32_t stream_flags, void* stream);
+/* dstream fp32 [M,D]: in = gradient of the residual stream after this block's attention branch, out = gradient before the block
+ * (in place); dx_bf16 its bf16 copy.  dstream == NULL: the gradient stream is kept in bf16 only -- dx_bf16 is read as the incoming
+ * gradient and overwritten with the outgoing one (the forward stream stays fp32 or fp16; profiles/r2_stream_precision.md, model D).
+ * dh bf16 [M,D] scratch; dw fp32 [3D,D], db fp32 [3D], dgamma / dbeta fp32 [D];
+ * dx_colsum (optional fp32 [D]) = column sums of the produced gradient (= d c_proj.bias of the block below). */
+int32_t vipant_ln_qkv_bwd(const uint16_t* dqkv, const uint16_t* w_qkv_t, const uint16_t* h, const void* x, const float* mean,
+                          const float* rstd, const float* gamma, float* dstream, uint16_t* dx_bf16, uint16_t* dh, float* dw,
+                          float* db, float* dgamma, float* dbeta, float* dx_colsum, int64_t M, int64_t D, void* workspace,
+                          size_t workspace_bytes, const vipant_fp8_plan* plan, int32_t stream_flags, void* stream);
+
+/* K4 -- out_proj (cvap/module/val.py:517, 520).  residual == NULL: out bf16 [M,N] = a . w^T + bias (the step's form: the add
+ * happens in the next LayerNorm pass; a == NULL with a plan: vipant_mha_fwd has left the operand's e4m3 form in the plan's scratch);
+ * residual fp32 [M,N]: out fp32 [M,N] = a . w^T + bias + residual (stand-alone form, plan == NULL only). */
+int32_t vipant_gemm_bias_residual_fwd(const uint16_t* a, const uint16_t* w, const float* bias, const float* residual, void* out,
+                                      int64_t M, int64_t N, int64_t K, const vipant_fp8_plan* plan, void* stream);
+/* da bf16 [M,K] = dy . w (w_t = w^T, [K,N]); dw fp32 [N,K] = dy^T a.  (d bias = column sums of dy: see dx_colsum above.) */
+int32_t vipant_gemm_bias_residual_bwd(const uint16_t* dy, const uint16_t* w_t, const uint16_t* a, uint16_t* da, float* dw,
+                                      int64_t M, int64_t N, int64_t K, void* workspace, size_t workspace_bytes,
+                                      const vipant_fp8_plan* plan, void* stream);
+
+/* K5 -- ln_2 + c_fc + QuickGELU + c_proj (cvap/module/val.py:502-506, 521; clip/model.py:163-165).
+ * h bf16 [M,D] = LN(x (+ add)); u = h . w_fc^T + b_fc; g bf16 [M,4D] = u * sigmoid(1.702 u); dcode uint8 [M,4D] = 8-bit code of
+ * QuickGELU'(u) (all the backward needs of u: VIPANT_EPI_QUICKGELU_D8); y bf16 [M,D] = g . w_proj^T + b_proj. */
+int32_t vipant_ln_mlp_quickgelu_fwd(const void* x, const uint16_t* add, void* x_out, const float* gamma, const float* beta,
+                                    const uint16_t* w_fc, const float* b_fc, const uint16_t* w_proj, const float* b_proj,
+                                    uint16_t* h, float* mean, float* rstd, uint8_t* dcode, uint16_t* g, uint16_t* y, int64_t M,
+                                    int64_t D, const vipant_fp8_plan* plan, int32_t stream_flags, void* stream);
+/* dcode, g again from the saved h (activation-memory plan `running.recompute_mlp`). */
+int32_t vipant_mlp_quickgelu_recompute(const uint16_t* h, const uint16_t* w_fc, const float* b_fc, uint8_t* dcode, uint16_t* g,
+                                       int64_t M, int64_t D, const vipant_fp8_plan* plan, void* stream);
+/* dy bf16 [M,D] = gradient of the MLP branch output (= bf16 copy of the stream gradient); dstream as in vipant_ln_qkv_bwd;
+ * du bf16 [M,4D], dh bf16 [M,D] scratch; dw_proj fp32 [D,4D], dw_fc fp32 [4D,D], db_fc fp32 [4D];
+ * dx_colsum (optional fp32 [D]) = d out_proj.bias. */
+int32_t vipant_ln_mlp_quickgelu_bwd(const uint16_t* dy, const uint16_t* w_proj_t, const uint16_t* w_fc_t, const uint8_t* dcode,
+                                    const uint16_t* g, const uint16_t* h, const void* x, const float* mean, const float* rstd,
+                                    const float* gamma, float* dstream, uint16_t* dx_bf16, uint16_t* du, uint16_t* dh,
+                                    float* dw_proj, float* dw_fc, float* db_fc, float* dgamma, float* dbeta, float* dx_colsum,
+                                    int64_t M, int64_t D, void* workspace, size_t workspace_bytes, const vipant_fp8_plan* plan,
+                                    int32_t stream_flags, void* stream);
 
 /* K1 -- ViTPreEncoder.forward (cvap/module/val.py:228-259): patch conv as im2col + contraction, cls token, positional table,
  * ln_pre.  x fp32 [b,C,T,F]; conv_w fp32 [Dw,Cw,ph,pw] (mean_channels != 0: the Cw stored channels are averaged, val.py:236-244);
- * scratch / saved: w_eff bf16 [Dw,kcols], patches bf16 [b*P,kcols], pe: unused since round 3 (may be NULL), tokens fp32 [b*S,Dw] (kcols =
+ * scratch / saved: w_eff bf16 [Dw,kcols], patches bf16 [b*P,kcols], tokens fp32 [b*S,Dw] (kcols =
  * (mean_channels ? 1 : Cw)*ph*pw, P = nrow*ncol, S = P+1); out fp32 [b*S,Dw] = the residual stream; mean / rstd fp32 [b*S]. */
 int32_t vipant_patch_embed_ln_fwd(const float* x, const float* conv_w, const float* cls, const float* pos, const float* gamma,
-                                  const float* beta, uint16_t* w_eff, uint16_t* patches, float* pe, float* tokens, float* out,
+                                  const float* beta, uint16_t* w_eff, uint16_t* patches, float* tokens, float* out,
                                   float* mean, float* rstd, int64_t b, int64_t C, int64_t T, int64_t F, int64_t Dw, int64_t Cw,
                                   int64_t ph, int64_t pw, int64_t sh, int64_t sw, int32_t mean_channels, void* stream);
 size_t vipant_patch_embed_ln_bwd_workspace_bytes(int64_t b, int64_t P, int64_t Dw, int64_t kcols);
@@ -546,9 +516,10 @@ int32_t vipant_patch_embed_ln_bwd(const void* dout, int32_t dout_bf16, const flo
                                   int64_t Cw, int64_t khw, int32_t mean_channels, void* workspace, size_t workspace_bytes,
                                   void* stream);
 
-/* K6 -- ViTPostEncoder.forward + MetaHead's normalisation (cvap/module/val.py:288-289, clip_head.py:117-118):
- * feat fp32 [batch,E] = LN(x[b, idx_b]) . proj (proj_t = proj^T bf16 [E,D]); idx == NULL reads row 0 (cls) in place, else the
- * rows are gathered into `rows` fp32 [batch,D]; normalized != 0: out = feat / |feat|, norm fp32 [batch] (else out is unused). */
+/* K6 / K7 -- the read-outs: ViTPostEncoder.forward (cvap/module/val.py:288-289) and GPTPostEncoder.forward (val.py:136-146) +
+ * MetaHead's normalisation (clip_head.py:117-118).  (GPTPreEncoder.forward, val.py:109-122, is vipant_embed_tokens.)
+ * feat fp32 [batch,E] = LN(x[b, idx_b]) . proj (proj_t = proj^T bf16 [E,D]); idx == NULL reads row 0 (cls) in place, else (the
+ * end-of-text rows) the rows are gathered into `rows` fp32 [batch,D]; normalized != 0: out = feat / |feat|, norm fp32 [batch] (else out is unused). */
 int32_t vipant_cls_ln_proj_l2norm_fwd(const float* x, const int64_t* idx, const float* gamma, const float* beta,
                                       const uint16_t* proj_t, float* rows, uint16_t* y, float* mean, float* rstd, float* feat,
                                       float* out, float* norm, int64_t batch, int64_t S, int64_t D, int64_t E, int32_t normalized,
@@ -564,14 +535,6 @@ int32_t vipant_cls_ln_proj_l2norm_bwd(const float* dout, const float* out, const
                                       const float* gamma, const uint16_t* proj, uint16_t* dfeat, uint16_t* dy, float* drows,
                                       float* dx, float* dproj, float* dgamma, float* dbeta, int64_t batch, int64_t S, int64_t D,
                                       int64_t E, int32_t normalized, void* workspace, size_t workspace_bytes, void* stream);
-
-/* K7 -- GPTPreEncoder.forward (cvap/module/val.py:109-122) and GPTPostEncoder.forward (val.py:136-146) of the frozen text tower. */
-int32_t vipant_embed_gather_pos_fwd(const int64_t* tokens, const float* table, const float* pos, float* x, int64_t* eot,
-                                    int64_t b, int64_t L, int64_t D, void* stream);
-int32_t vipant_eot_ln_proj_l2norm_fwd(const float* x, const int64_t* eot, const float* gamma, const float* beta,
-                                      const uint16_t* proj_t, float* rows, uint16_t* y, float* mean, float* rstd, float* feat,
-                                      float* out, float* norm, int64_t batch, int64_t L, int64_t D, int64_t E, int32_t normalized,
-                                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,8 +24,36 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/vipant_hip.h but not exported"
     assert sorted(_ffi.PROTOTYPES.keys()) == syms, set(_ffi.PROTOTYPES) ^ set(syms)
-    assert lib.vipant_version() == 100
+    assert _ffi.ABI_VERSION == lib.vipant_version() == 101
     assert lib.vipant_last_error() is not None
+
+
+def test_library_exports_no_undeclared_symbol():
+    """The other direction: every `vipant_*` function the library exports is declared in the header (a forwarder that lost its
+    declaration, a debug export outside its #ifdef)."""
+    import subprocess
+    from vipant_amd import _ffi, build
+    build.build(verbose=False)
+    out = subprocess.run(["nm", "-D", "--defined-only", _ffi.LIB_PATH], check=True, stdout=subprocess.PIPE, text=True).stdout
+    exported = {f[-1] for f in map(str.split, out.splitlines()) if f and f[-1].startswith("vipant_")}
+    assert len(exported) >= 28
+    assert exported <= set(header_symbols()), sorted(exported - set(header_symbols()))
+
+
+def test_library_of_another_abi_version_is_refused(monkeypatch):
+    """Argument lists changed under existing names at version 101: a library that reports another version (VIPANT_HIP_LIB pointing at
+    an older build) must be refused before any of its functions can be called."""
+    from vipant_amd import _ffi, build
+    build.build(verbose=False)
+    found = _ffi.lib().vipant_version()
+    monkeypatch.setattr(_ffi, "ABI_VERSION", found + 1)
+    monkeypatch.setattr(_ffi, "_lib", None)
+    with pytest.raises(_ffi.VipantError) as e:
+        _ffi.lib()
+    assert str(found) in str(e.value) and str(found + 1) in str(e.value) and _ffi.LIB_PATH in str(e.value)
+    assert _ffi._lib is None
+    monkeypatch.undo()
+    assert _ffi.lib().vipant_version() == _ffi.ABI_VERSION
 
 
 def test_argument_counts_match_header():
@@ -54,9 +82,9 @@ def test_bad_arguments_are_reported_not_executed():
     with pytest.raises(_ffi.VipantError, match="K%64"):
         _ffi.call("vipant_gemm_nt", 16, 100, 16, 100, 16, 64, None, None, 1.0, 4, 64, 100, 0, None)
     with pytest.raises(_ffi.VipantError, match="empty problem"):
-        _ffi.call("vipant_mha_fwd", 16, 16, 16, 1, 0, 12, 0, None)
+        _ffi.call("vipant_mha_fwd", 16, 16, 16, None, None, 1, 0, 12, 0, None)
     with pytest.raises(_ffi.VipantError, match="16-byte aligned"):
-        _ffi.call("vipant_mha_fwd", 8, 16, 16, 1, 100, 12, 0, None)
+        _ffi.call("vipant_mha_fwd", 8, 16, 16, None, None, 1, 100, 12, 0, None)
     with pytest.raises(_ffi.VipantError, match="workspace"):
         _ffi.call("vipant_infonce_fwd_bwd", 16, 16, 16, 0.0, 16, None, None, None, 1.0, 64, 512, 0, 64, None, 0, None)
     with pytest.raises(_ffi.VipantError, match="K % 128"):
@@ -71,7 +99,7 @@ def test_bad_arguments_are_reported_not_executed():
     with pytest.raises(_ffi.VipantError, match="K <= 8192"):
         _ffi.call("vipant_quant_e4m3_rows", 16, 16384, 16, 16384, 16, 4, 16384, None)
     with pytest.raises(_ffi.VipantError, match="go together"):
-        _ffi.call("vipant_layernorm_fwd_e4m3", 16, 768, 16, 16, 16, None, 16, 16, 4, 768, None, None, 16, None, 0, None)
+        _ffi.call("vipant_layernorm_fwd", 16, 768, 16, 16, 16, None, 16, 16, 4, 768, None, None, 16, None, 0, None)
 
 
 def test_no_cpu_fallback():

@@ -344,8 +344,8 @@ def test_block_stack_with_e4m3_contractions_tracks_the_bf16_stack(ops):
 
 @pytest.mark.parametrize("D", [768, 1024])
 def test_layernorm_fused_block_quantisation_is_the_standalone_one(ops, D):
-    """vipant_layernorm_bwd_e4m3: the bytes and block scales written beside the bf16 gradient are exactly what vipant_quant_e4m3_mx
-    makes of it (so fusing the pass changes nothing downstream); vipant_layernorm_fwd_e4m3: the stated static-scale form of its output."""
+    """vipant_layernorm_bwd with q / qscale: the bytes and block scales written beside the bf16 gradient are exactly what vipant_quant_e4m3_mx
+    makes of it (so fusing the pass changes nothing downstream); vipant_layernorm_fwd with q / qscale: the stated static-scale form of its output."""
     M = 1000
     x = rnd(M, D, seed=31) * torch.exp2(torch.randint(-4, 5, (M, 1), device=DEV).float())
     add = rnd(M, D, seed=32).to(torch.bfloat16)
@@ -356,7 +356,7 @@ def test_layernorm_fused_block_quantisation_is_the_standalone_one(ops, D):
     q = torch.empty(M, D, dtype=torch.uint8, device=DEV)
     qs = torch.empty(ops.query("vipant_mx_scale_bytes", M, D), dtype=torch.uint8, device=DEV)
     st = torch.cuda.current_stream().cuda_stream
-    ops.call("vipant_layernorm_fwd_e4m3", x.data_ptr(), D, gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), None, mean.data_ptr(),
+    ops.call("vipant_layernorm_fwd", x.data_ptr(), D, gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), None, mean.data_ptr(),
              rstd.data_ptr(), M, D, add.data_ptr(), xs.data_ptr(), q.data_ptr(), qs.data_ptr(), 0, st)
     # forward (round 6): STATIC scales -- one per 32-column block, the same for every row, from sqrt(D) |gamma| + |beta| (a normalised
     # row cannot exceed it): block-uniform, nothing saturates, and the bytes are y / 2^e rounded to e4m3
@@ -374,20 +374,21 @@ def test_layernorm_fused_block_quantisation_is_the_standalone_one(ops, D):
     dxb2 = dxb.clone()
     dg, db, cs = (torch.empty(D, device=DEV) for _ in range(3))
     ws = ops.scratch("ln_bwd", ops.query("vipant_layernorm_bwd_workspace_bytes", M, D), x.device)
-    ops.call("vipant_layernorm_bwd_e4m3", dy.data_ptr(), 2, xs.data_ptr(), D, mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+    ops.call("vipant_layernorm_bwd", dy.data_ptr(), 2, xs.data_ptr(), D, mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
              dxb.data_ptr(), None, D, dxb.data_ptr(), dg.data_ptr(), db.data_ptr(), cs.data_ptr(), 0, M, D, ws.data_ptr(), ws.numel(),
              q.data_ptr(), qs.data_ptr(), st)
     q_ref, s_ref = ops.quant_e4m3_mx(dxb)
     assert torch.equal(q, q_ref) and torch.equal(mx_scales(ops, qs, M, D), mx_scales(ops, s_ref, M, D))
     ops.call("vipant_layernorm_bwd", dy.data_ptr(), 2, xs.data_ptr(), D, mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
-             dxb2.data_ptr(), None, D, dxb2.data_ptr(), dg.data_ptr(), db.data_ptr(), cs.data_ptr(), 0, M, D, ws.data_ptr(), ws.numel(), st)
+             dxb2.data_ptr(), None, D, dxb2.data_ptr(), dg.data_ptr(), db.data_ptr(), cs.data_ptr(), 0, M, D, ws.data_ptr(), ws.numel(),
+             None, None, st)
     assert torch.equal(dxb, dxb2)
 
 
 @pytest.mark.parametrize("batch,S,H,causal", [(3, 316, 12, False), (2, 306, 16, False), (60, 316, 12, False), (2, 77, 8, True),
                                               (3, 200, 4, False), (1, 428, 4, False), (2, 50, 2, False)])
 def test_attention_fused_block_quantisation_is_the_standalone_one(ops, batch, S, H, causal):
-    """vipant_mha_{fwd,bwd}_e4m3: `out` / `dqkv` are bit for bit those of the plain entry points, and the e4m3 bytes + block scales
+    """vipant_mha_{fwd,bwd} with the e4m3 outputs: `out` / `dqkv` are bit for bit those of the calls without them, and the e4m3 bytes + block scales
     written beside them are exactly vipant_quant_e4m3_mx of those tensors -- whoever wrote them: at 224 < S <= 320 without mask the
     streamed backward's dK | dV staging (720 problems: with the ticket walk) with the dQ columns by the column-range pass; the
     stand-alone pass enqueued behind the kernel for the forward and for the other backward shapes (causal, S = 200, S = 428, S = 50)."""

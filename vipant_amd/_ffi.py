@@ -16,6 +16,7 @@ import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIPANT_HIP_LIB") or os.path.join(_HERE, "lib", "libvipant_hip.so")   # override: A/B timing of builds
+ABI_VERSION = 101             # what vipant_version() of a library with the argument lists of PROTOTYPES returns
 
 EPI_BF16, EPI_F32, EPI_RESIDUAL_F32, EPI_QUICKGELU, EPI_DQUICKGELU, EPI_SCALE_F32, EPI_QUICKGELU_D8, EPI_DQUICKGELU_D8 = range(8)
 EPI_FEW_ROWS = 0x100          # VIPANT_EPI_FEW_ROWS: one row per item of a batch (read-out rows): the 64 x 64 split-K kernel
@@ -47,16 +48,12 @@ PROTOTYPES = {
     "vipant_gemm_tn_pair": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _sz, _p]),
     "vipant_colsum_workspace_bytes": (_sz, [_i64, _i64]),
     "vipant_colsum_bf16": (_i32, [_p, _i64, _p, _i64, _i64, _i32, _p, _sz, _p]),
-    "vipant_layernorm_fwd": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "vipant_residual_add": (_i32, [_p, _p, _p, _i64, _i32, _p]),
     "vipant_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i64]),
-    "vipant_layernorm_fwd_e4m3": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i32, _p]),
-    "vipant_layernorm_bwd_e4m3": (_i32, [_p, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _i64, _i64, _p, _sz, _p, _p, _p]),
-    "vipant_layernorm_bwd": (_i32, [_p, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _i64, _i64, _p, _sz, _p]),
-    "vipant_mha_fwd": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _p]),
-    "vipant_mha_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
-    "vipant_mha_fwd_e4m3": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
-    "vipant_mha_bwd_e4m3": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
+    "vipant_layernorm_fwd": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i32, _p]),
+    "vipant_layernorm_bwd": (_i32, [_p, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _i64, _i64, _p, _sz, _p, _p, _p]),
+    "vipant_mha_fwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
+    "vipant_mha_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
     "vipant_mha_rows_fwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
     "vipant_mha_rows_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
     "vipant_rows_ctx_fwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p]),
@@ -82,7 +79,6 @@ PROTOTYPES = {
     "vipant_cast_bf16": (_i32, [_p, _p, _p, _i64, _i64, _p]),
     "vipant_conv_weight_prep": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p]),
     "vipant_im2col": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p]),
-    "vipant_assemble_tokens": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "vipant_assemble_tokens_bwd": (_i32, [_p, _p, _p, _p, _i32, _i64, _i64, _i64, _p]),
     "vipant_conv_weight_grad": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p]),
     "vipant_l2norm_fwd": (_i32, [_p, _p, _p, _i64, _i64, _p]),
@@ -100,28 +96,19 @@ PROTOTYPES = {
     "vipant_fbank": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _f32, _f32, _p, _sz, _p]),
     # fused operator set (vipant_amd/csrc/block.hip)
     "vipant_block_workspace_bytes": (_sz, [_i64, _i64]),
-    "vipant_ln_qkv_fwd": (_i32, [_p] * 11 + [_i64, _i64, _p]),
-    "vipant_ln_qkv_fwd_e4m3": (_i32, [_p] * 11 + [_i64, _i64, _p, _i32, _p]),
-    "vipant_ln_qkv_bwd_e4m3": (_i32, [_p] * 15 + [_i64, _i64, _p, _sz, _p, _i32, _p]),
-    "vipant_gemm_bias_residual_fwd_e4m3": (_i32, [_p] * 5 + [_i64, _i64, _i64, _p, _p]),
-    "vipant_gemm_bias_residual_bwd_e4m3": (_i32, [_p] * 5 + [_i64, _i64, _i64, _p, _sz, _p, _p]),
-    "vipant_ln_mlp_quickgelu_fwd_e4m3": (_i32, [_p] * 15 + [_i64, _i64, _p, _i32, _p]),
-    "vipant_mlp_quickgelu_recompute_e4m3": (_i32, [_p] * 5 + [_i64, _i64, _p, _p]),
-    "vipant_ln_mlp_quickgelu_bwd_e4m3": (_i32, [_p] * 20 + [_i64, _i64, _p, _sz, _p, _i32, _p]),
-    "vipant_ln_qkv_bwd": (_i32, [_p] * 15 + [_i64, _i64, _p, _sz, _p]),
-    "vipant_gemm_bias_residual_fwd": (_i32, [_p] * 5 + [_i64, _i64, _i64, _p]),
-    "vipant_gemm_bias_residual_bwd": (_i32, [_p] * 5 + [_i64, _i64, _i64, _p, _sz, _p]),
-    "vipant_ln_mlp_quickgelu_fwd": (_i32, [_p] * 15 + [_i64, _i64, _p]),
-    "vipant_mlp_quickgelu_recompute": (_i32, [_p] * 5 + [_i64, _i64, _p]),
-    "vipant_ln_mlp_quickgelu_bwd": (_i32, [_p] * 20 + [_i64, _i64, _p, _sz, _p]),
-    "vipant_patch_embed_ln_fwd": (_i32, [_p] * 13 + [_i64] * 10 + [_i32, _p]),
+    "vipant_ln_qkv_fwd": (_i32, [_p] * 11 + [_i64, _i64, _p, _i32, _p]),
+    "vipant_ln_qkv_bwd": (_i32, [_p] * 15 + [_i64, _i64, _p, _sz, _p, _i32, _p]),
+    "vipant_gemm_bias_residual_fwd": (_i32, [_p] * 5 + [_i64, _i64, _i64, _p, _p]),
+    "vipant_gemm_bias_residual_bwd": (_i32, [_p] * 5 + [_i64, _i64, _i64, _p, _sz, _p, _p]),
+    "vipant_ln_mlp_quickgelu_fwd": (_i32, [_p] * 15 + [_i64, _i64, _p, _i32, _p]),
+    "vipant_mlp_quickgelu_recompute": (_i32, [_p] * 5 + [_i64, _i64, _p, _p]),
+    "vipant_ln_mlp_quickgelu_bwd": (_i32, [_p] * 20 + [_i64, _i64, _p, _sz, _p, _i32, _p]),
+    "vipant_patch_embed_ln_fwd": (_i32, [_p] * 12 + [_i64] * 10 + [_i32, _p]),
     "vipant_patch_embed_ln_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "vipant_patch_embed_ln_bwd": (_i32, [_p, _i32] + [_p] * 13 + [_i64] * 5 + [_i32, _p, _sz, _p]),
     "vipant_cls_ln_proj_l2norm_fwd": (_i32, [_p] * 12 + [_i64] * 4 + [_i32, _p]),
     "vipant_cls_ln_proj_l2norm_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "vipant_cls_ln_proj_l2norm_bwd": (_i32, [_p] * 18 + [_i64] * 4 + [_i32, _p, _sz, _p]),
-    "vipant_embed_gather_pos_fwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
-    "vipant_eot_ln_proj_l2norm_fwd": (_i32, [_p] * 12 + [_i64] * 4 + [_i32, _p]),
     "vipant_lars_workspace_bytes": (_sz, [_i64]),
     "vipant_lars_step": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _f32, _f32, _f32, _p, _sz, _p]),
     # Barlow Twins loss head (vipant_amd/csrc/barlow.hip)
@@ -154,7 +141,11 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: the HIP hot path is not built (run `python -m vipant_amd.build`); "
                 "there is no CPU fallback")
         handle = C.CDLL(LIB_PATH)
-        older = "VIPANT_HIP_LIB" in os.environ       # an A/B run against another (possibly older) build: its missing entry points fail at use
+        found = handle.vipant_version()      # (ctypes' default `int f(void)` fits: no prototype is attached before this check)
+        if found != ABI_VERSION:             # same names, other argument lists: no call may reach such a library
+            raise VipantError(f"{LIB_PATH} has ABI version {found}, this package needs {ABI_VERSION} "
+                              "(rebuild with `python -m vipant_amd.build`)")
+        older = "VIPANT_HIP_LIB" in os.environ       # an A/B run against another build of this ABI version: entry points it lacks fail at use
         for name, (res, args) in PROTOTYPES.items():
             if older and not hasattr(handle, name):
                 continue

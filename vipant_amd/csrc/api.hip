@@ -19,7 +19,7 @@ void vipant_set_error(const char* fmt, ...) {
 
 extern "C" const char* vipant_last_error(void) { return g_err; }
 
-extern "C" int32_t vipant_version(void) { return 100; }  // 0.1.0
+extern "C" int32_t vipant_version(void) { return 101; }  // the ABI version (_ffi.ABI_VERSION): changes with any argument list
 
 extern "C" int32_t vipant_device_check(void) {
     int dev = 0;

@@ -1350,60 +1350,48 @@ int32_t dispatch(const MhaArgs& a, hipStream_t s) {
     return launch_stream<CAUSAL, BWD>(a, s);       // S > 384: chunks of the other dimension streamed through LDS
 }
 
-int32_t check(const void* qkv, int64_t batch, int64_t S, int64_t H) {
+// (q8, q8_scale): the optional e4m3 form of the result
+int32_t check(const char* op, const void* qkv, const void* q8, const void* q8_scale, int64_t batch, int64_t S, int64_t H) {
     VIPANT_REQUIRE(batch > 0 && S > 0 && H > 0, VIPANT_EBADSHAPE, "mha: empty problem");
     VIPANT_REQUIRE((uintptr_t)qkv % 16 == 0, VIPANT_EALIGN, "mha: qkv must be 16-byte aligned");
     VIPANT_REQUIRE(batch * H < (1ll << 31), VIPANT_EBADSHAPE, "mha: too many (batch, head) problems");
+    VIPANT_REQUIRE((q8 == nullptr) == (q8_scale == nullptr) && (q8 == nullptr || H % 2 == 0), VIPANT_EBADSHAPE,
+                   "%s: the e4m3 bytes and their scales go together and need an even head count", op);
     return VIPANT_OK;
 }
 
 }  // namespace
 
-extern "C" int32_t vipant_mha_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int64_t batch, int64_t S, int64_t H,
-                                  int32_t causal, void* stream) {
-    if (int32_t e = check(qkv, batch, S, H)) return e;
-    MhaArgs a{(const bf16_t*)qkv, (bf16_t*)out, lse, nullptr, nullptr, nullptr, (int)batch, (int)S, (int)H, 0};
-    return causal ? dispatch<true, false>(a, (hipStream_t)stream) : dispatch<false, false>(a, (hipStream_t)stream);
-}
-
-extern "C" int32_t vipant_mha_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
-                                  float* delta, uint16_t* dqkv, int64_t batch, int64_t S, int64_t H, int32_t causal,
-                                  void* stream) {
-    if (int32_t e = check(qkv, batch, S, H)) return e;
-    MhaArgs a{(const bf16_t*)qkv, (bf16_t*)out, const_cast<float*>(lse), (const bf16_t*)dout, delta, (bf16_t*)dqkv,
-              (int)batch, (int)S, (int)H, 0};
-    return causal ? dispatch<true, true>(a, (hipStream_t)stream) : dispatch<false, true>(a, (hipStream_t)stream);
-}
-
-// The same two with the e4m3 + MX-scale form of the result beside the bf16 one (BASELINE configs[4]: the out_proj / in_proj^T
-// contractions read it; csrc/block.hip).  The streamed single-pass backward emits it from its problem tail for the dK | dV columns,
-// which leave through LDS as whole rows (dQ leaves inside the hand-scheduled steps and takes the stand-alone pass, a third of the
-// bytes); every other backward shape, and the forward, run the stand-alone pass over the whole result.  (The forward's emission was
-// built and measured in round 5 -- bit-identical, 744 -> 985 us at the ViT-L shape against 744 + 197 for kernel + pass: the kernel is
-// issue-bound and its 16-byte row segments make poor stores -- and taken out again; profiles/r5_cfg5_mx.md.)
-extern "C" int32_t vipant_mha_fwd_e4m3(const uint16_t* qkv, uint16_t* out, float* lse, uint8_t* oq, uint8_t* oq_scale, int64_t batch,
-                                       int64_t S, int64_t H, int32_t causal, void* stream) {
-    if (int32_t e = check(qkv, batch, S, H)) return e;
-    VIPANT_REQUIRE(oq != nullptr && oq_scale != nullptr && H % 2 == 0, VIPANT_EBADSHAPE, "mha_fwd_e4m3: need both outputs and an even head count");
+// out_q / out_scale resp. dqkv_q / dqkv_scale (both or neither): the e4m3 + MX-scale form of the result beside the bf16 one (BASELINE
+// configs[4]: the out_proj / in_proj^T contractions read it; csrc/block.hip).  The streamed single-pass backward emits it from its
+// problem tail for the dK | dV columns, which leave through LDS as whole rows (dQ leaves inside the hand-scheduled steps and takes
+// the stand-alone pass, a third of the bytes); every other backward shape, and the forward, run the stand-alone pass over the whole
+// result.  (The forward's emission was built and measured in round 5 -- bit-identical, 744 -> 985 us at the ViT-L shape against
+// 744 + 197 for kernel + pass: the kernel is issue-bound and its 16-byte row segments make poor stores -- and taken out again;
+// profiles/r5_cfg5_mx.md.)
+extern "C" int32_t vipant_mha_fwd(const uint16_t* qkv, uint16_t* out, float* lse, uint8_t* out_q, uint8_t* out_scale, int64_t batch,
+                                  int64_t S, int64_t H, int32_t causal, void* stream) {
+    if (int32_t e = check("mha_fwd", qkv, out_q, out_scale, batch, S, H)) return e;
     MhaArgs a{(const bf16_t*)qkv, (bf16_t*)out, lse, nullptr, nullptr, nullptr, (int)batch, (int)S, (int)H, 0};
     if (int32_t e = causal ? dispatch<true, false>(a, (hipStream_t)stream) : dispatch<false, false>(a, (hipStream_t)stream)) return e;
+    if (out_q == nullptr) return VIPANT_OK;
     // (block-uniform scales, round 6: the same pass, and the weight-gradient contraction of out_proj reads the form as it is)
-    return vipant_quant_e4m3_mx32(out, H * 64, oq, H * 64, oq_scale, batch * S, H * 64, stream);
+    return vipant_quant_e4m3_mx32(out, H * 64, out_q, H * 64, out_scale, batch * S, H * 64, stream);
 }
 
-extern "C" int32_t vipant_mha_bwd_e4m3(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                                       uint16_t* dqkv, uint8_t* gq, uint8_t* gq_scale, int64_t batch, int64_t S, int64_t H,
-                                       int32_t causal, void* stream) {
-    if (int32_t e = check(qkv, batch, S, H)) return e;
-    VIPANT_REQUIRE(gq != nullptr && gq_scale != nullptr && H % 2 == 0, VIPANT_EBADSHAPE, "mha_bwd_e4m3: need both outputs and an even head count");
+extern "C" int32_t vipant_mha_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
+                                  uint16_t* dqkv, uint8_t* dqkv_q, uint8_t* dqkv_scale, int64_t batch, int64_t S, int64_t H,
+                                  int32_t causal, void* stream) {
+    if (int32_t e = check("mha_bwd", qkv, dqkv_q, dqkv_scale, batch, S, H)) return e;
     MhaArgs a{(const bf16_t*)qkv, (bf16_t*)out, const_cast<float*>(lse), (const bf16_t*)dout, delta, (bf16_t*)dqkv,
               (int)batch, (int)S, (int)H, 0};
     const int64_t D = H * 64;
-    const bool fused = !causal && S > 224 && S <= 320;         // mha_bwd1s_kernel (launch_bwd)
-    if (fused) { a.gq = gq; a.gq_scale = gq_scale; }
+    const bool fused = dqkv_q != nullptr && !causal && S > 224 && S <= 320;         // mha_bwd1s_kernel (launch_bwd)
+    if (fused) { a.gq = dqkv_q; a.gq_scale = dqkv_scale; }
     if (int32_t e = causal ? dispatch<true, true>(a, (hipStream_t)stream) : dispatch<false, true>(a, (hipStream_t)stream)) return e;
+    if (dqkv_q == nullptr) return VIPANT_OK;
     // (the columns this pass makes -- dQ, or all three thirds -- get block-uniform scales; the streamed kernel's dK | dV stay row-wise)
-    return vipant_quant_e4m3_mx32_cols(dqkv, 3 * D, gq, 3 * D, gq_scale, batch * S, fused ? D : 3 * D, 3 * D / 128, 0, stream);
+    return vipant_quant_e4m3_mx32_cols(dqkv, 3 * D, dqkv_q, 3 * D, dqkv_scale, batch * S, fused ? D : 3 * D, 3 * D / 128, 0, stream);
 }
 
 #ifdef VIPANT_ATTN_STAMPS

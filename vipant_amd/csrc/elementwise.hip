@@ -177,21 +177,6 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ x
 }
 
 // ---- token assembly ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void assemble_kernel(const float* __restrict__ patches, const float* __restrict__ cls,
-                                                       const float* __restrict__ pos, float* __restrict__ tokens, int64_t b,
-                                                       int P, int D) {
-    const int S = P + 1, d4 = D / 4;
-    const int64_t total = b * S * d4;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c = (int)(i % d4) * 4;
-        const int64_t row = i / d4;
-        const int s = (int)(row % S);
-        const int64_t bi = row / S;
-        const f32x4 base = s == 0 ? *(const f32x4*)(cls + c) : *(const f32x4*)(patches + (bi * P + s - 1) * D + c);
-        *(f32x4*)(tokens + row * D + c) = base + *(const f32x4*)(pos + (int64_t)s * D + c);
-    }
-}
-
 // tokens[item * S, :] = cls + pos[0, :]: the class-token rows (the patch rows come from vipant_gemm_nt_tokens)
 __global__ __launch_bounds__(256) void cls_rows_kernel(const float* __restrict__ cls, const float* __restrict__ pos,
                                                        float* __restrict__ tokens, int64_t b, int64_t S, int D) {
@@ -713,15 +698,6 @@ extern "C" int32_t vipant_im2col(const float* x, uint16_t* out, int64_t b, int64
     const int64_t total = b * nrow * ncol * (C * ph * pw / 8);
     hipLaunchKernelGGL(im2col_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)out,
                        (int)b, (int)C, (int)T, (int)F, (int)ph, (int)pw, (int)sh, (int)sw, nrow, ncol, vec_ok);
-    VIPANT_LAUNCH_CHECK();
-    return VIPANT_OK;
-}
-
-extern "C" int32_t vipant_assemble_tokens(const float* patches, const float* cls, const float* pos, float* tokens,
-                                          int64_t b, int64_t P, int64_t D, void* stream) {
-    VIPANT_REQUIRE(b > 0 && P > 0 && D % 4 == 0, VIPANT_EBADSHAPE, "assemble_tokens: bad shape");
-    hipLaunchKernelGGL(assemble_kernel, dim3(grid_for(b * (P + 1) * D / 4, 256)), dim3(256), 0, (hipStream_t)stream,
-                       patches, cls, pos, tokens, b, (int)P, (int)D);
     VIPANT_LAUNCH_CHECK();
     return VIPANT_OK;
 }

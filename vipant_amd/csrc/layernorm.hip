@@ -261,10 +261,9 @@ int ln_blocks(int64_t M) {
 
 }  // namespace
 
-extern "C" int32_t vipant_layernorm_fwd_e4m3(const void* x, int64_t ldx, const float* gamma, const float* beta,
-                                             uint16_t* y, float* y_f32, float* mean, float* rstd, int64_t M, int64_t D,
-                                             const uint16_t* add, void* sum_out, uint8_t* q, uint8_t* qscale, int32_t stream_flags,
-                                             void* stream) {
+extern "C" int32_t vipant_layernorm_fwd(const void* x, int64_t ldx, const float* gamma, const float* beta, uint16_t* y,
+                                        float* y_f32, float* mean, float* rstd, int64_t M, int64_t D, const uint16_t* add,
+                                        void* sum_out, uint8_t* q, uint8_t* qscale, int32_t stream_flags, void* stream) {
     VIPANT_REQUIRE((q == nullptr) == (qscale == nullptr), VIPANT_EBADSHAPE, "layernorm_fwd: q and qscale go together");
     VIPANT_REQUIRE(M > 0 && D > 0 && D % 256 == 0 && D <= 1024, VIPANT_EBADSHAPE,
                    "layernorm_fwd: D must be a multiple of 256 up to 1024 (D=%ld)", (long)D);
@@ -301,21 +300,15 @@ extern "C" int32_t vipant_layernorm_fwd_e4m3(const void* x, int64_t ldx, const f
     return VIPANT_OK;
 }
 
-extern "C" int32_t vipant_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta,
-                                        uint16_t* y, float* y_f32, float* mean, float* rstd, int64_t M, int64_t D,
-                                        const uint16_t* add, float* sum_out, void* stream) {
-    return vipant_layernorm_fwd_e4m3(x, ldx, gamma, beta, y, y_f32, mean, rstd, M, D, add, sum_out, nullptr, nullptr, 0, stream);
-}
-
 extern "C" size_t vipant_layernorm_bwd_workspace_bytes(int64_t M, int64_t D) {
     return (size_t)ln_blocks(M) * 3 * (size_t)D * sizeof(float);
 }
 
-extern "C" int32_t vipant_layernorm_bwd_e4m3(const void* dy, int32_t flags, const void* x, int64_t ldx,
-                                             const float* mean, const float* rstd, const float* gamma, const void* dres,
-                                             float* dx_f32, int64_t lddx, uint16_t* dx_bf16, float* dgamma, float* dbeta,
-                                             float* dx_colsum, int32_t accumulate, int64_t M, int64_t D, void* workspace,
-                                             size_t workspace_bytes, uint8_t* q, uint8_t* qscale, void* stream) {
+extern "C" int32_t vipant_layernorm_bwd(const void* dy, int32_t flags, const void* x, int64_t ldx, const float* mean,
+                                        const float* rstd, const float* gamma, const void* dres, float* dx_f32, int64_t lddx,
+                                        uint16_t* dx_bf16, float* dgamma, float* dbeta, float* dx_colsum, int32_t accumulate,
+                                        int64_t M, int64_t D, void* workspace, size_t workspace_bytes, uint8_t* q, uint8_t* qscale,
+                                        void* stream) {
     VIPANT_REQUIRE((q == nullptr) == (qscale == nullptr), VIPANT_EBADSHAPE, "layernorm_bwd: q and qscale go together");
     VIPANT_REQUIRE(M > 0 && D > 0 && D % 256 == 0 && D <= 1024, VIPANT_EBADSHAPE,
                    "layernorm_bwd: D must be a multiple of 256 up to 1024 (D=%ld)", (long)D);
@@ -356,13 +349,4 @@ extern "C" int32_t vipant_layernorm_bwd_e4m3(const void* dy, int32_t flags, cons
                        (const float*)partial, blocks, (int)D, dgamma, dbeta, dx_colsum, accumulate);
     VIPANT_LAUNCH_CHECK();
     return VIPANT_OK;
-}
-
-extern "C" int32_t vipant_layernorm_bwd(const void* dy, int32_t flags, const void* x, int64_t ldx,
-                                        const float* mean, const float* rstd, const float* gamma, const void* dres,
-                                        float* dx_f32, int64_t lddx, uint16_t* dx_bf16, float* dgamma, float* dbeta,
-                                        float* dx_colsum, int32_t accumulate, int64_t M, int64_t D, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-    return vipant_layernorm_bwd_e4m3(dy, flags, x, ldx, mean, rstd, gamma, dres, dx_f32, lddx, dx_bf16, dgamma, dbeta, dx_colsum,
-                                     accumulate, M, D, workspace, workspace_bytes, nullptr, nullptr, stream);
 }

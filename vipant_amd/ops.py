@@ -227,7 +227,7 @@ def layernorm_fwd(x: torch.Tensor, gamma, beta, *, want_bf16=True, want_f32=Fals
     mean, rstd = _stats(M, x.device)
     xsum = torch.empty((M, D), dtype=F16 if sum_f16 else F32, device=x.device) if (add is not None and want_sum) else None
     flags = (_ffi.STREAM_IN_F16 if x.dtype == F16 else 0) | (_ffi.STREAM_OUT_F16 if sum_f16 else 0)
-    call("vipant_layernorm_fwd_e4m3", x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), _ptr(y), _ptr(y32),
+    call("vipant_layernorm_fwd", x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), _ptr(y), _ptr(y32),
          mean.data_ptr(), rstd.data_ptr(), M, D, _ptr(add), _ptr(xsum), None, None, flags, _stream())
     if add is not None:
         return y, y32, mean, rstd, xsum
@@ -259,7 +259,7 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, mean, rstd, gamma, *, dres=
     ws = scratch("ln_bwd", query("vipant_layernorm_bwd_workspace_bytes", M, D), x.device)
     call("vipant_layernorm_bwd", dy.data_ptr(), int(dy.dtype == F32) | (_ffi.LN_X_F16 if x.dtype == F16 else 0), x.data_ptr(), ldx, mean.data_ptr(),
          rstd.data_ptr(), gamma.data_ptr(), _ptr(dres), _ptr(dx), lddx, _ptr(dx_bf16), dgamma.data_ptr(),
-         dbeta.data_ptr(), _ptr(dx_colsum), int(accumulate), M, D, ws.data_ptr(), ws.numel(), _stream())
+         dbeta.data_ptr(), _ptr(dx_colsum), int(accumulate), M, D, ws.data_ptr(), ws.numel(), None, None, _stream())
 
 
 def mha_fwd(qkv: torch.Tensor, batch: int, S: int, H: int, causal: bool, q8=None):
@@ -267,11 +267,8 @@ def mha_fwd(qkv: torch.Tensor, batch: int, S: int, H: int, causal: bool, q8=None
     _need(qkv, BF16, "mha_fwd.qkv")
     out = torch.empty((batch * S, H * 64), dtype=BF16, device=qkv.device)
     lse = torch.empty((batch, H, S), dtype=F32, device=qkv.device)
-    if q8 is not None:
-        call("vipant_mha_fwd_e4m3", qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), q8[0].data_ptr(), q8[1].data_ptr(), batch, S, H,
-             int(causal), _stream())
-    else:
-        call("vipant_mha_fwd", qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), batch, S, H, int(causal), _stream())
+    oq, oscale = q8 if q8 is not None else (None, None)
+    call("vipant_mha_fwd", qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), _ptr(oq), _ptr(oscale), batch, S, H, int(causal), _stream())
     return out, lse
 
 
@@ -279,12 +276,9 @@ def mha_bwd(qkv, out, dout, lse, batch: int, S: int, H: int, causal: bool, q8=No
     """q8 = (bytes, block scales): also leave the e4m3 form of `dqkv` there (rows of 3 * H * 64 bytes)."""
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
-    if q8 is not None:
-        call("vipant_mha_bwd_e4m3", qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-             dqkv.data_ptr(), q8[0].data_ptr(), q8[1].data_ptr(), batch, S, H, int(causal), _stream())
-    else:
-        call("vipant_mha_bwd", qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-             dqkv.data_ptr(), batch, S, H, int(causal), _stream())
+    gq, gscale = q8 if q8 is not None else (None, None)
+    call("vipant_mha_bwd", qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(), dqkv.data_ptr(),
+         _ptr(gq), _ptr(gscale), batch, S, H, int(causal), _stream())
     return dqkv
 
 
@@ -506,7 +500,7 @@ class PatchEmbedFn(torch.autograd.Function):
         mean, rstd = _stats(b * S, dev)
         call("vipant_patch_embed_ln_fwd", x.data_ptr(), conv_w.detach().contiguous().data_ptr(),
              cls.detach().contiguous().data_ptr(), pos.detach().contiguous().data_ptr(), ln_w.detach().data_ptr(),
-             ln_b.detach().data_ptr(), w_eff.data_ptr(), patches.data_ptr(), None, tok.data_ptr(), out.data_ptr(),
+             ln_b.detach().data_ptr(), w_eff.data_ptr(), patches.data_ptr(), tok.data_ptr(), out.data_ptr(),
              mean.data_ptr(), rstd.data_ptr(), b, Cx, T, Fq, D, Cw, ph, pw, sh, sw, int(mean_ch), _stream())
         ctx.save_for_backward(patches, tok, mean, rstd, ln_w)
         ctx.meta = (b, P, D, Cw, ph * pw, mean_ch, tuple(conv_w.shape), tuple(pos.shape))
@@ -698,24 +692,24 @@ def _block_fwd(s: _Stack, b: _Block, x, y_prev, p, wb, wq, tmp):
     u, g = (b.u, b.g) if s.keep_mlp else (tmp.u, tmp.g)
     # ln_1 (+ residual add of the previous block's MLP branch: x <- x + y2_prev) + in_proj
     xs = new(D, s.sdt) if y_prev is not None else None
-    call("vipant_ln_qkv_fwd_e4m3", x.data_ptr(), _ptr(y_prev), _ptr(xs), ln1w.data_ptr(), ln1b.data_ptr(), wqkv_b.data_ptr(),
+    call("vipant_ln_qkv_fwd", x.data_ptr(), _ptr(y_prev), _ptr(xs), ln1w.data_ptr(), ln1b.data_ptr(), wqkv_b.data_ptr(),
          bqkv.data_ptr(), _ptr(b.h1), b.mean1.data_ptr(), b.rstd1.data_ptr(), b.qkv.data_ptr(), M, D,
          C.byref(fp8_plan(q_qkv, None, b.h1q or tmp.act)) if fp8 else None, s.sflags(x), st)
     b.x = x = xs if xs is not None else x
     q8 = (b.oq or tmp.act) if emit_o else None
     b.o, b.lse = mha_fwd(b.qkv, s.batch, s.S, H, s.causal, q8=q8)
-    call("vipant_gemm_bias_residual_fwd_e4m3", None if q8 else b.o.data_ptr(), wo_b.data_ptr(), bo.data_ptr(), None, y1.data_ptr(),
+    call("vipant_gemm_bias_residual_fwd", None if q8 else b.o.data_ptr(), wo_b.data_ptr(), bo.data_ptr(), None, y1.data_ptr(),
          M, D, D, C.byref(fp8_plan(q_o, None, q8 or tmp.act)) if fp8 else None, st)
     # ln_2 (+ residual add of the attention branch) + c_fc + QuickGELU + c_proj
     b.x1 = new(D, s.sdt)
     if "gemm_nt" in KERNEL_PROBE and not fp8:     # bench.py times the c_fc launch alone: the same three launches, issued one by one
-        call("vipant_layernorm_fwd_e4m3", x.data_ptr(), D, ln2w.data_ptr(), ln2b.data_ptr(), b.h2.data_ptr(), None,
+        call("vipant_layernorm_fwd", x.data_ptr(), D, ln2w.data_ptr(), ln2b.data_ptr(), b.h2.data_ptr(), None,
              b.mean2.data_ptr(), b.rstd2.data_ptr(), M, D, y1.data_ptr(), b.x1.data_ptr(), None, None, s.sflags(x), st)
         gemm_nt(b.h2, wfc_b, g, bias=bfc, aux=u, epi=EPI_QUICKGELU_D8)
         gemm_nt(g, wpr_b, y2, bias=bpr, epi=EPI_BF16)
     else:
         only_q = fp8 and not s.keep_mlp        # c_proj's operand is all that is wanted of g: neither g nor the codes are written
-        call("vipant_ln_mlp_quickgelu_fwd_e4m3", x.data_ptr(), y1.data_ptr(), b.x1.data_ptr(), ln2w.data_ptr(), ln2b.data_ptr(),
+        call("vipant_ln_mlp_quickgelu_fwd", x.data_ptr(), y1.data_ptr(), b.x1.data_ptr(), ln2w.data_ptr(), ln2b.data_ptr(),
              wfc_b.data_ptr(), bfc.data_ptr(), wpr_b.data_ptr(), bpr.data_ptr(), _ptr(b.h2), b.mean2.data_ptr(),
              b.rstd2.data_ptr(), None if only_q else u.data_ptr(), None if (only_q or g is None) else g.data_ptr(), y2.data_ptr(), M, D,
              C.byref(fp8_plan(q_fc, q_pr, b.h2q or tmp.act, emit=b.gq or tmp.emit)) if fp8 else None, s.sflags(x), st)
@@ -733,7 +727,7 @@ def _rows_block_fwd(s: _Stack, b: _RowsBlock, x, y_prev, p, wb, tmp):
     # (training: the last block keeps its per-token activations for the read-out rows only)
     b.h1, (b.mean1, b.rstd1) = (new(D), _stats(M, dev)) if s.train else (tmp.h1, tmp.stats)
     xs = new(D, s.sdt) if y_prev is not None else None
-    call("vipant_layernorm_fwd_e4m3", x.data_ptr(), D, ln1w.data_ptr(), ln1b.data_ptr(), b.h1.data_ptr(), None,
+    call("vipant_layernorm_fwd", x.data_ptr(), D, ln1w.data_ptr(), ln1b.data_ptr(), b.h1.data_ptr(), None,
          b.mean1.data_ptr(), b.rstd1.data_ptr(), M, D, _ptr(y_prev), _ptr(xs), None, None, s.sflags(x), st)
     b.x = x = xs if xs is not None else x
     b.h1_r = gather_rows(b.h1, ridx, batch, S)
@@ -762,7 +756,7 @@ def _rows_block_fwd(s: _Stack, b: _RowsBlock, x, y_prev, p, wb, tmp):
     # the two roundings (fp16 stream, bf16 branch output) the full block would give them
     b.x1_r, b.h2_r, b.u_r, b.g_r = new(D, F32, batch), new(D, rows=batch), new(4 * D, torch.uint8, batch), new(4 * D, rows=batch)
     b.mean2_r, b.rstd2_r = _stats(batch, dev)
-    call("vipant_layernorm_fwd_e4m3", x_r.data_ptr(), D, ln2w.data_ptr(), ln2b.data_ptr(), b.h2_r.data_ptr(), None,
+    call("vipant_layernorm_fwd", x_r.data_ptr(), D, ln2w.data_ptr(), ln2b.data_ptr(), b.h2_r.data_ptr(), None,
          b.mean2_r.data_ptr(), b.rstd2_r.data_ptr(), batch, D, y1_r.data_ptr(), b.x1_r.data_ptr(), None, None,
          _ffi.STREAM_IN_F16 if x_r.dtype == F16 else 0, st)
     gemm_nt(b.h2_r, wfc_b, b.g_r, bias=bfc, aux=b.u_r, epi=EPI_QUICKGELU_D8, few_rows=True)
@@ -780,7 +774,7 @@ def _block_bwd(s: _Stack, b: _Block, p, lg: _LayerGrads, lg_below: Optional[_Lay
         # (e4m3 weight gradients: the recomputation leaves g's e4m3 form -- the same epilogue, the same bytes as a forward that keeps
         # it -- and no bf16 g)
         u, g, keep = tmp.u, tmp.g, tmp.gq
-        call("vipant_mlp_quickgelu_recompute_e4m3", None if fp8 else b.h2.data_ptr(), b.wfc_b.data_ptr(), bfc.data_ptr(), u.data_ptr(),
+        call("vipant_mlp_quickgelu_recompute", None if fp8 else b.h2.data_ptr(), b.wfc_b.data_ptr(), bfc.data_ptr(), u.data_ptr(),
              None if kq else g.data_ptr(), M, D, C.byref(fp8_plan(b.q_fc, None, b.h2q, emit=keep)) if fp8 else None, st)
         if not kq:
             b.h2q = None        # read by the recomputation alone
@@ -789,7 +783,7 @@ def _block_bwd(s: _Stack, b: _Block, p, lg: _LayerGrads, lg_below: Optional[_Lay
     keep1, keep2 = (b.h1q, b.h2q) if kq else (None, None)     # h1, h2 (and g) as the e4m3 forms the forward kept
     # MLP half: c_proj^T + QuickGELU', c_fc^T, both weight gradients, ln_2 backward (+ residual gradient);
     # the produced stream gradient is also d(out_proj output): its column sum is d out_proj.bias
-    call("vipant_ln_mlp_quickgelu_bwd_e4m3", dx_b.data_ptr(), wpr_t.data_ptr(), wfc_t.data_ptr(), u.data_ptr(),
+    call("vipant_ln_mlp_quickgelu_bwd", dx_b.data_ptr(), wpr_t.data_ptr(), wfc_t.data_ptr(), u.data_ptr(),
          None if keep else g.data_ptr(), None if keep2 else b.h2.data_ptr(), b.x1.data_ptr(), b.mean2.data_ptr(), b.rstd2.data_ptr(),
          ln2w.data_ptr(), _ptr(dx), dx_b.data_ptr(), _ptr(tmp.du), tmp.dh.data_ptr(), d_wpr.data_ptr(), d_wfc.data_ptr(),
          d_bfc.data_ptr(), d_ln2w.data_ptr(), d_ln2b.data_ptr(), d_bo.data_ptr(), M, D, ws.data_ptr(), ws.numel(),
@@ -797,12 +791,12 @@ def _block_bwd(s: _Stack, b: _Block, p, lg: _LayerGrads, lg_below: Optional[_Lay
          _ffi.STREAM_IN_F16 if b.x1.dtype == F16 else 0, st)
     # attention half: out_proj^T, attention core, in_proj^T + ln_1 backward; the produced stream gradient is
     # d(c_proj output) of the block below: its column sum is that block's d c_proj.bias
-    call("vipant_gemm_bias_residual_bwd_e4m3", dx_b.data_ptr(), wo_t.data_ptr(), b.o.data_ptr(), tmp.do.data_ptr(), d_wo.data_ptr(),
+    call("vipant_gemm_bias_residual_bwd", dx_b.data_ptr(), wo_t.data_ptr(), b.o.data_ptr(), tmp.do.data_ptr(), d_wo.data_ptr(),
          M, D, D, ws.data_ptr(), ws.numel(),
          C.byref(fp8_plan(tq_o, None, tmp.act, dyq, emit=tmp.emit, tn=s.tn8, keep=b.oq)) if fp8 else None, st)
     q8 = tmp.act if (fp8 and H % 2 == 0 and ATTN_EMIT) else None
     dqkv = mha_bwd(b.qkv, b.o, tmp.do, b.lse, s.batch, s.S, H, s.causal, q8=q8)
-    call("vipant_ln_qkv_bwd_e4m3", dqkv.data_ptr(), wqkv_t.data_ptr(), None if keep1 else b.h1.data_ptr(), b.x.data_ptr(),
+    call("vipant_ln_qkv_bwd", dqkv.data_ptr(), wqkv_t.data_ptr(), None if keep1 else b.h1.data_ptr(), b.x.data_ptr(),
          b.mean1.data_ptr(), b.rstd1.data_ptr(), ln1w.data_ptr(), _ptr(dx), dx_b.data_ptr(), tmp.dh.data_ptr(), d_wqkv.data_ptr(),
          d_bqkv.data_ptr(), d_ln1w.data_ptr(), d_ln1b.data_ptr(), lg_below.views[11].data_ptr() if lg_below is not None else None,
          M, D, ws.data_ptr(), ws.numel(), C.byref(fp8_plan(tq_qkv, None, tmp.act, dyq, emit=tmp.emit, tn=s.tn8, keep=keep1)) if fp8 else None,
@@ -818,7 +812,7 @@ def _rows_block_bwd(s: _Stack, b: _RowsBlock, p, lg: _LayerGrads, lg_below: Opti
     wqkv_t, wo_t, wfc_t, wpr_t = b.wt
     d_ln1w, d_ln1b, d_wqkv, d_bqkv, d_wo, d_bo, d_ln2w, d_ln2b, d_wfc, d_bfc, d_wpr, d_bpr = lg.views
     du_r, dh_r, do_r = s.new(4 * D, rows=batch), s.new(D, rows=batch), s.new(D, rows=batch)
-    call("vipant_ln_mlp_quickgelu_bwd_e4m3", dxr_b.data_ptr(), wpr_t.data_ptr(), wfc_t.data_ptr(), b.u_r.data_ptr(),
+    call("vipant_ln_mlp_quickgelu_bwd", dxr_b.data_ptr(), wpr_t.data_ptr(), wfc_t.data_ptr(), b.u_r.data_ptr(),
          b.g_r.data_ptr(), b.h2_r.data_ptr(), b.x1_r.data_ptr(), b.mean2_r.data_ptr(), b.rstd2_r.data_ptr(), ln2w.data_ptr(), None,
          dxr_b.data_ptr(), du_r.data_ptr(), dh_r.data_ptr(), d_wpr.data_ptr(), d_wfc.data_ptr(), d_bfc.data_ptr(),
          d_ln2w.data_ptr(), d_ln2b.data_ptr(), d_bo.data_ptr(), batch, D, ws.data_ptr(), ws.numel(), None,
@@ -854,7 +848,7 @@ def _rows_block_bwd(s: _Stack, b: _RowsBlock, p, lg: _LayerGrads, lg_below: Opti
     gemm_tn(dq_r, b.h1_r, d_wqkv[:D], a_colsum=d_bqkv[:D], ws_name="block_bwd")
     # ln_1 backward on every token; the residual gradient of this block exists on the read-out rows only
     dx_b = torch.empty((M, D), dtype=BF16, device=dev)
-    call("vipant_layernorm_bwd_e4m3", dh.data_ptr(), _ffi.LN_X_F16 if b.x.dtype == F16 else 0, b.x.data_ptr(), D,
+    call("vipant_layernorm_bwd", dh.data_ptr(), _ffi.LN_X_F16 if b.x.dtype == F16 else 0, b.x.data_ptr(), D,
          b.mean1.data_ptr(), b.rstd1.data_ptr(), ln1w.data_ptr(), None, None, D, dx_b.data_ptr(), d_ln1w.data_ptr(),
          d_ln1b.data_ptr(), lg_below.views[11].data_ptr() if lg_below is not None else None, 0, M, D, ws.data_ptr(),
          ws.numel(), None, None, st)
@@ -1030,9 +1024,9 @@ class ReadoutFn(torch.autograd.Function):
         feat = torch.empty((batch, E), dtype=F32, device=dev)
         out = torch.empty_like(feat) if normalized else feat
         norm = torch.empty((batch,), dtype=F32, device=dev) if normalized else None
-        call("vipant_eot_ln_proj_l2norm_fwd" if idx is not None else "vipant_cls_ln_proj_l2norm_fwd", x.data_ptr(), _ptr(idx),
-             ln_w.detach().data_ptr(), ln_b.detach().data_ptr(), proj_t.data_ptr(), _ptr(rows), y.data_ptr(), mean.data_ptr(),
-             rstd.data_ptr(), feat.data_ptr(), out.data_ptr(), _ptr(norm), batch, S, D, E, int(bool(normalized)), _stream())
+        call("vipant_cls_ln_proj_l2norm_fwd", x.data_ptr(), _ptr(idx), ln_w.detach().data_ptr(), ln_b.detach().data_ptr(),
+             proj_t.data_ptr(), _ptr(rows), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), feat.data_ptr(), out.data_ptr(), _ptr(norm),
+             batch, S, D, E, int(bool(normalized)), _stream())
         if train:
             ctx.save_for_backward(x, idx, rows, y, mean, rstd, ln_w, proj_b, out, norm)
             ctx.meta = (batch, S, D, E, bool(normalized))
@@ -1076,7 +1070,7 @@ def embed_tokens(tokens: torch.Tensor, table: torch.Tensor, pos: torch.Tensor):
     assert pos.shape[0] >= L
     x = torch.empty((b * L, D), dtype=F32, device=tokens.device)
     eot = torch.empty((b,), dtype=I64, device=tokens.device)
-    call("vipant_embed_gather_pos_fwd", tokens.data_ptr(), table.detach().data_ptr(), pos.detach().contiguous().data_ptr(),
+    call("vipant_embed_tokens", tokens.data_ptr(), table.detach().data_ptr(), pos.detach().contiguous().data_ptr(),
          x.data_ptr(), eot.data_ptr(), b, L, D, _stream())
     return x, eot
 
