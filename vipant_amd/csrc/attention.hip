@@ -1261,10 +1261,14 @@ int32_t launch_stream(const MhaArgs& a, hipStream_t s) {
 template <int NT>
 int32_t launch_bwd1s(const MhaArgs& a, hipStream_t s);
 
-// No environment switch selects a kernel here (round 5): every kernel in this file is the only one for its shapes, and
-// tests/test_kernels_gpu.py::test_mha reaches each of them -- forward (S <= 384), single-pass streamed backward (224 < S <= 320, no
-// mask), two-pass backward (causal / other S), streaming kernels (S > 384).  Variants that were measured and not kept are text
-// under tools/probes/ (mha_bwd1_resident, attention_wide, mha_fwd2_variant).
+// No environment switch selects a kernel here (round 5): every kernel in this file is the only one for its shapes -- forward
+// (S <= 384), single-pass streamed backward (224 < S <= 320, no mask), two-pass backward (causal / other S), streaming kernels
+// (S > 384).  tests/test_kernels_gpu.py::test_mha runs only S = 16, 20c, 31, 50, 77c, 306, 316 and four streaming lengths, i.e. the
+// EDGE = 2 instances of NT = 2, 4, 6, 20; what reaches EVERY instance below -- each (NT, CAUSAL, EDGE) forward, the 4- and 8-wave
+// two-pass backward causal and not, mha_bwd1s_kernel in both of its edge ranges, the streaming kernels -- is
+// tests/test_attention_gpu.py::test_instance_sweep, whose select() restates dispatch() and whose parameter list is checked against
+// it on the CPU: a bucket bound or an instantiation changed here has to be changed there.  Variants that were measured and not
+// kept are text under tools/probes/ (mha_bwd1_resident, attention_wide, mha_fwd2_variant).
 
 template <int NT, bool CAUSAL, int NW, int EDGE>
 int32_t launch_fwd_nw(const MhaArgs& a, hipStream_t s) {
