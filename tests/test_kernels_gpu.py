@@ -400,7 +400,7 @@ def test_mha(ops, batch, S, H, causal):
 def test_mha_bwd_ticket_walk_equals_static_walk(ops, monkeypatch, batch, H, S):
     """Round 5: the persistent attention backward (mha_bwd1s_kernel, one workgroup per CU) draws its third and later problems from the
     stream's ticket counter when batch * heads > 2 x CUs (720, 513 and 516 problems here: long queues, a single drawn problem, four).
-    Which workgroup computes a problem must not matter: bit-identical to the static stride (VIPANT_GEMM_VARIANT bit 22), alone and with
+    Which workgroup computes a problem must not matter: bit-identical to the static stride (VIPANT_GEMM_VARIANT bit 22, _ffi.SW_STATIC_WALK), alone and with
     CUs held by the probe kernel (tools/probes/comm_shadow.hip) on a second stream, repeatedly (the counters must be back at zero for every launch, also when a
     ticket-walk NT contraction runs in between on the same stream)."""
     D = H * 64
@@ -411,7 +411,8 @@ def test_mha_bwd_ticket_walk_equals_static_walk(ops, monkeypatch, batch, H, S):
     side = torch.cuda.Stream()
     a = rnd(40448, 768, seed=13, dtype=torch.bfloat16); w = rnd(768, 768, seed=14, dtype=torch.bfloat16, scale=0.03)
     c = torch.empty(40448, 768, dtype=torch.bfloat16, device=DEV)
-    monkeypatch.setenv("VIPANT_GEMM_VARIANT", "4194304")
+    from vipant_amd import _ffi
+    monkeypatch.setenv("VIPANT_GEMM_VARIANT", str(_ffi.SW_STATIC_WALK))
     ref = ops.mha_bwd(qkv, out, dout, lse, batch, S, H, False)
     assert torch.isfinite(ref.float()).all()
     monkeypatch.setenv("VIPANT_GEMM_VARIANT", "0")
@@ -912,7 +913,7 @@ def test_pingpong_kernels_are_repeatable_under_load(ops):
 def test_gemm_nt_ticket_walk_equals_static_walk(ops, monkeypatch, M, N, K, epi):
     """Round 5: the persistent NT kernels draw their tiles from per-XCD ticket queues (common.h) so that a workgroup whose CU is held
     by another stream's kernel -- the RCCL all-reduce of a gradient bucket -- costs 1/256 of a launch, not a round.  Which workgroup
-    computes a tile must not matter: bit-identical to the static-stride walk (VIPANT_GEMM_VARIANT bit 22), with the chip to itself
+    computes a tile must not matter: bit-identical to the static-stride walk (VIPANT_GEMM_VARIANT bit 22, _ffi.SW_STATIC_WALK), with the chip to itself
     and with 64 CUs held for 300 us / 24 CUs for 3 ms by the probe kernel (tools/probes/comm_shadow.hip) on a second stream (late workgroups, some finding their
     queue empty); every element written each time (the ticket block must be back at zero after every launch)."""
     a = rnd(M, K, seed=61, dtype=torch.bfloat16); b = rnd(N, K, seed=62, dtype=torch.bfloat16, scale=K ** -0.5)
@@ -933,7 +934,8 @@ def test_gemm_nt_ticket_walk_equals_static_walk(ops, monkeypatch, M, N, K, epi):
         ops.gemm_nt(a, b, c, aux=code_in, epi=ops.EPI_DQUICKGELU_D8)
         return (c,)
 
-    monkeypatch.setenv("VIPANT_GEMM_VARIANT", "4194304")
+    from vipant_amd import _ffi
+    monkeypatch.setenv("VIPANT_GEMM_VARIANT", str(_ffi.SW_STATIC_WALK))
     ref = run()
     assert all(torch.isfinite(t.float()).all() for t in ref)
     monkeypatch.setenv("VIPANT_GEMM_VARIANT", "0")

@@ -6,7 +6,7 @@ GradSync.reduce_async would start the RCCL all-reduce.  Settings are interleaved
 
     python tools/comm_shadow.py [--steps 8] [--rounds 2] [--quick]
 
-walk:    ticket (default build) | static (VIPANT_GEMM_VARIANT bit 22: the round-4 static-stride tile walk of the NT kernels)
+walk:    ticket (default build) | static (VIPANT_GEMM_VARIANT bit 22, _ffi.SW_STATIC_WALK: the round-4 static-stride tile walk of the NT kernels)
 overlap: block (bucket per block, overlapping the backward) | step (one hand-over after the backward)
 """
 import argparse
@@ -80,7 +80,7 @@ def main():
             it[0] += 1
 
     def timed(walk, overlap, shadow):
-        os.environ["VIPANT_GEMM_VARIANT"] = "4194304" if walk == "static" else "0"
+        os.environ["VIPANT_GEMM_VARIANT"] = str(_ffi.SW_STATIC_WALK) if walk == "static" else "0"
         nwg, _, us = shadow.partition(":")
         sync.nwg, sync.min_us, sync.overlap = int(nwg), float(us or 0.0), overlap
         run(2)

@@ -60,10 +60,3 @@ print(f"variant={os.environ.get('VIPANT_GEMM_VARIANT', '0')}")
 for name, flops, fn in cases:
     med, best = timeit(fn)
     print(f"{name}: median {med * 1e3:8.1f} us  best {best * 1e3:8.1f} us  {flops / med / 1e9:7.1f} TFLOP/s")
-
-# prologue + epilogue share: same launch with K = 64 (one K-tile) against K = 768
-for name, K, fn in (("nt fc gelu K=64 ", 64, lambda: ops.gemm_nt(x768[:, :64], w_fc[:, :64], o3072, bias=bias3072, aux=u3072, epi=ops.EPI_QUICKGELU)),
-                    ("nt qkv bf16 K=64", 64, lambda: ops.gemm_nt(x768[:, :64], w_qkv[:, :64], o2304, bias=bias2304, epi=ops.EPI_BF16)),
-                    ("nt out res K=64 ", 64, lambda: ops.gemm_nt(x768[:, :64], w_o[:, :64], r768b, bias=bias768, aux=r768, epi=ops.EPI_RESIDUAL_F32))):
-    med, best = timeit(fn)
-    print(f"{name}: median {med * 1e3:8.1f} us  best {best * 1e3:8.1f} us")

@@ -1,14 +1,14 @@
 """Tile walk / schedule A/B on the two K = 768, N = 3072 launches of the step (c_fc + QuickGELU, QuickGELU'), alternating in one
 process; also checks the variants against each other bit for bit.  VIPANT_GEMM_VARIANT: 0 = shipped default (DEEP schedule on the
-column-grouped walk), 8388608 (bit 23) = the round-4 choice (grouped k-step for c_fc, plain DEEP for QuickGELU'), 2048 = grouped walk on the
-k-step schedule everywhere, 4096 = grouped nowhere."""
+column-grouped walk), SW_ROUND4_SCHEDULES (bit 23) = the round-4 choice (grouped k-step for c_fc, plain DEEP for QuickGELU'), SW_GROUPED_ALWAYS (bit 11) = grouped walk on the
+k-step schedule everywhere, SW_GROUPED_NEVER (bit 12) = grouped nowhere (names: vipant_amd/_ffi.py)."""
 import os
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vipant_amd import ops  # noqa: E402
+from vipant_amd import _ffi, ops  # noqa: E402
 
 dev = "cuda:0"
 M = 512 * 316
@@ -26,7 +26,7 @@ c_out = torch.empty(M, 3072, dtype=torch.uint8, device=dev)
 c_in = torch.randint(0, 256, (M, 3072), dtype=torch.uint8, device=dev)
 cases = [("c_fc  ", lambda: ops.gemm_nt(x768, w_fc, o3072, bias=b3072, aux=c_out, epi=ops.EPI_QUICKGELU_D8), lambda: (o3072.clone(), c_out.clone())),
          ("dgelu8", lambda: ops.gemm_nt(x768, w_fc, o3072, aux=c_in, epi=ops.EPI_DQUICKGELU_D8), lambda: (o3072.clone(),))]
-variants = ["0", "8388608", "2048", "4096"]
+variants = ["0", str(_ffi.SW_ROUND4_SCHEDULES), str(_ffi.SW_GROUPED_ALWAYS), str(_ffi.SW_GROUPED_NEVER)]
 
 
 def one(fn):

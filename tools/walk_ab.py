@@ -1,4 +1,4 @@
-"""Static-stride vs ticket walk of the persistent kernels (NT contractions, attention backward; VIPANT_GEMM_VARIANT bit 22), per launch shape of the VA step,
+"""Static-stride vs ticket walk of the persistent kernels (NT contractions, attention backward; VIPANT_GEMM_VARIANT bit 22, _ffi.SW_STATIC_WALK), per launch shape of the VA step,
 alternating in one process: python tools/walk_ab.py [rounds]"""
 import os
 import sys
@@ -6,7 +6,9 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vipant_amd import ops  # noqa: E402
+from vipant_amd import _ffi, ops  # noqa: E402
+
+STATIC = str(_ffi.SW_STATIC_WALK)
 
 dev = "cuda:0"
 M = 512 * 316
@@ -46,7 +48,7 @@ def one(fn):
 
 
 for name, fn in cases:
-    t = {"0": [], "4194304": []}
+    t = {"0": [], STATIC: []}
     for v in t:
         os.environ["VIPANT_GEMM_VARIANT"] = v
         fn(); fn()
@@ -56,5 +58,5 @@ for name, fn in cases:
             os.environ["VIPANT_GEMM_VARIANT"] = v
             t[v].append(one(fn))
     med = {v: sorted(x)[len(x) // 2] for v, x in t.items()}
-    print(f"{name}: ticket {med['0']:7.1f} us (best {min(t['0']):7.1f})   static {med['4194304']:7.1f} us (best {min(t['4194304']):7.1f})   "
-          f"delta {med['0'] - med['4194304']:+6.1f} us", flush=True)
+    print(f"{name}: ticket {med['0']:7.1f} us (best {min(t['0']):7.1f})   static {med[STATIC]:7.1f} us (best {min(t[STATIC]):7.1f})   "
+          f"delta {med['0'] - med[STATIC]:+6.1f} us", flush=True)

@@ -24,6 +24,8 @@ STREAM_FEW_ROWS = 0x100
 STREAM_ACT_Q = 0x200
 STREAM_IN_F16, STREAM_OUT_F16 = 1, 2          # VIPANT_STREAM_*: precision of the residual stream inside the transformer stack
 LN_DY_F32, LN_DRES_BF16, LN_X_F16 = 1, 2, 4
+# VIPANT_GEMM_VARIANT switches that Python code sets (tests, tools/); csrc/switches.h names every bit, DESIGN.md section 9 has the table
+SW_GROUPED_ALWAYS, SW_GROUPED_NEVER, SW_STATIC_WALK, SW_ROUND4_SCHEDULES = 1 << 11, 1 << 12, 1 << 22, 1 << 23
 
 _p, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
 

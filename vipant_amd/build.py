@@ -178,7 +178,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
                 isa_guard.CHECKS[base](isa_path(base))
             except AssertionError as e:
                 os.remove(_obj(src))            # no object, no library: a build whose hand-counted waits do not hold must not ship
-                raise RuntimeError(f"ISA guard of {base} failed on this toolchain ({e}); VIPANT_GEMM_VARIANT=4194304 selects the static "
+                from ._ffi import SW_STATIC_WALK
+                raise RuntimeError(f"ISA guard of {base} failed on this toolchain ({e}); VIPANT_GEMM_VARIANT={SW_STATIC_WALK} (SW_STATIC_WALK, bit 22) selects the static "
                                    "tile walk of the NT kernels, the attention guard has no fallback") from e
         for name, u in usage.items():
             if u.get("VGPRs Spill", 0) or u.get("ScratchSize [bytes/lane]", 0):

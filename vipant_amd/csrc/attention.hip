@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "attn_common.h"
+#include "switches.h"
 
 using namespace vipant_attn;
 
@@ -1314,9 +1315,8 @@ int32_t launch_bwd1s(const MhaArgs& a, hipStream_t s) {
     }
     const int nprob = a.batch * a.H, cus = device_cus();       // one persistent workgroup per CU
     MhaArgs t = a;
-    // ticket walk when a workgroup has problems beyond its two static ones (bit 22 of VIPANT_GEMM_VARIANT: static, for A/B runs)
-    const char* var = getenv("VIPANT_GEMM_VARIANT");
-    if (nprob > 2 * cus && !(var && (atoi(var) & 4194304))) {
+    // ticket walk when a workgroup has problems beyond its two static ones (VIPANT_SW_STATIC_WALK: static, for A/B runs)
+    if (nprob > 2 * cus && !(vipant_switches() & VIPANT_SW_STATIC_WALK)) {
         t.tk = vipant_ticket_block(s, &t.tk_other);
         if (!t.tk) return VIPANT_EHIP;
     }

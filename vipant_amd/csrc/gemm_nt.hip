@@ -7,10 +7,14 @@
 // fragment reads are bank-conflict free (swizzle applied on the DMA source address and on the read
 // address: the LDS image of a DMA is lane-linear), v_mfma_f32_16x16x32_bf16 with the operands swapped
 // (D = B_tile . A_tile^T) so that every lane ends up holding 4 consecutive output columns of one row.
-#include <stdlib.h>
-
+//
+// Three kernel families live here: the plain kernel (one tile per workgroup, the two-stage main loop of nt_core.h; every fp32 epilogue,
+// and the bf16 ones when the output cannot be staged or K = 64), the persistent ping-pong kernel (bf16-output epilogues, K >= 128,
+// bf16 or e4m3 operands: what the step runs) and the few-rows kernel (64 x 64 tiles, K split over the waves).  Which instance a
+// launch reaches is decided in nt_select.h; the instance lists in front of vipant_gemm_nt map that decision to a template.
 #include "common.h"
 #include "nt_core.h"
+#include "nt_select.h"
 
 namespace {
 
@@ -21,7 +25,7 @@ struct GemmNT {
     int64_t lda, ldb, ldc;
     int M, N, K;
     float alpha;
-    int dbg;   // VIPANT_GEMM_VARIANT (timing experiments only): bit 0 = skip the epilogue stores
+    int dbg;   // VIPANT_GEMM_VARIANT (switches.h; timing experiments only): bit 0 = skip the epilogue stores
     // fp8 operands only: E8M0 exponents (value = e4m3 * 2^(byte - 127)) -- A: one per 32 consecutive k of a row, in the MX layout of
     // common.h; B (a weight matrix): one per row
     const uint8_t* sa; const uint8_t* sb;
@@ -112,8 +116,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(GemmNT p) {
     }
 }
 
-// Stage the 256x256 accumulator tile through a 64 KiB LDS area and write it out as whole rows (16 B per lane),
-// applying the epilogue on the way.  Uses raw s_barrier + lgkmcnt waits only, so LDS-DMA prefetches in flight survive.
+// the bias of a tile's columns, in the accumulator layout (the ping-pong kernel fetches it ahead of its epilogue)
 template <int EPI>
 __device__ __forceinline__ void load_bias(const GemmNT& p, int cn0, int wn, int fq, f32x4 (&bv)[4]) {
 #pragma unroll
@@ -121,213 +124,6 @@ __device__ __forceinline__ void load_bias(const GemmNT& p, int cn0, int wn, int 
         const int n4 = cn0 + wn * 64 + j * 16 + fq * 4;
         bv[j] = (EPI != VIPANT_EPI_DQUICKGELU && EPI != VIPANT_EPI_DQUICKGELU_D8 && p.bias != nullptr && n4 < p.N) ? *(const f32x4*)(p.bias + n4)
                                                                                  : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-}
-
-template <int EPI>
-__device__ __forceinline__ void staged_epilogue(const GemmNT& p, f32x4 (&acc)[8][4], char* stg, int cm0, int cn0, int wm,
-                                                int wn, int frow, int fq, int tid, const f32x4 (&bv)[4]) {
-    if (EPI == VIPANT_EPI_RESIDUAL_F32) {
-        // fp32 tile: 4 rounds of 64 rows x 1 KiB; 16-B chunk index XOR (row & 7)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (wm == (q >> 1)) {
-#pragma unroll
-                for (int ii = 0; ii < 4; ++ii) {
-                    const int i = (q & 1) * 4 + ii;
-                    const int row = ii * 16 + frow;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int ch = (wn * 16 + j * 4 + fq) ^ (row & 7);
-                        *(f32x4*)(stg + row * 1024 + ch * 16) = acc[i][j] + bv[j];
-                    }
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int idx = t * 512 + tid;
-                const int row = idx >> 6, ch = idx & 63;
-                const int m = cm0 + q * 64 + row, n = cn0 + ch * 4;
-                if (m < p.M && n < p.N) {
-                    const f32x4 v = *(const f32x4*)(stg + row * 1024 + ((ch ^ (row & 7)) << 4));
-                    const int64_t o = (int64_t)m * p.ldc + n;
-                    *(f32x4*)((float*)p.C + o) = v + *(const f32x4*)((const float*)p.aux + o);
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-    } else {
-        // bf16 tile: 2 rounds of 128 rows x 512 B; 16-B chunk index XOR (row & 7)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            if (wm == h) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int row = i * 16 + frow;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int col = wn * 64 + j * 16 + fq * 4;
-                        const int ch = (col >> 3) ^ (row & 7);
-                        *(bf16x4*)(stg + row * 512 + ch * 16 + (col & 4) * 2) = f32x4_to_bf16x4(acc[i][j] + bv[j]);
-                    }
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int idx = t * 512 + tid;
-                const int row = idx >> 5, ch = idx & 31;
-                const int m = cm0 + h * 128 + row, n = cn0 + ch * 8;
-                if (m < p.M && n < p.N) {
-                    const bf16x8 v = *(const bf16x8*)(stg + row * 512 + ((ch ^ (row & 7)) << 4));
-                    const int64_t o = (int64_t)m * p.ldc + n;
-                    if (EPI == VIPANT_EPI_BF16) {
-                        *(bf16x8*)((bf16_t*)p.C + o) = v;
-                    } else if (EPI == VIPANT_EPI_QUICKGELU) {
-                        *(bf16x8*)((bf16_t*)p.aux + o) = v;
-                        bf16x8 g;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float u = (float)v[e];
-                            g[e] = (bf16_t)(u * quickgelu_gate(u));
-                        }
-                        *(bf16x8*)((bf16_t*)p.C + o) = g;
-                    } else {  // VIPANT_EPI_DQUICKGELU
-                        const bf16x8 u8 = *(const bf16x8*)((const bf16_t*)p.aux + o);
-                        bf16x8 d;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float u = (float)u8[e];
-                            const float sg = quickgelu_gate(u);
-                            d[e] = (bf16_t)((float)v[e] * (sg * (1.0f + 1.702f * u * (1.0f - sg))));
-                        }
-                        *(bf16x8*)((bf16_t*)p.C + o) = d;
-                    }
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Persistent variant for the large token-major contractions (M >> 256).  Measured on MI355X (tools/gemm_bench.py):
-// the 2-stage main loop alone sustains ~1.1 PFLOP/s, but with K = 768 a tile's epilogue (8-byte partial-line
-// stores straight from the accumulator layout) plus its un-overlapped prologue cost more than its 12 K-steps.
-// Here each workgroup walks a list of tiles and
-//   * stages the output tile through LDS (XOR-swizzled) so that global stores are whole 512-B / 1-KiB rows,
-//     16 B per lane;  QuickGELU and its derivative are applied on the way out of LDS, so `u` is staged once;
-//   * issues the LDS-DMA for the NEXT tile's first K-step before the epilogue, into the stage buffer the
-//     epilogue does not use, so the prologue latency and the store drain overlap (raw s_barrier in the epilogue:
-//     __syncthreads() would drain the DMA).
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_nt_persistent_kernel(GemmNT p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int frow = lane & 15, fq = lane >> 4, fs = (lane >> 1) & 7;
-
-    const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-    const int ntiles = ntm * ntn;
-    const int G = gridDim.x;                                   // multiple of 8
-    const int lane_pos = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);   // XCD-contiguous position in a round
-
-    uint32_t voffA[4], voffB[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = (wave * 4 + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        voffA[i] = (uint32_t)(r * p.lda * 2 + c * 16);
-        voffB[i] = (uint32_t)(r * p.ldb * 2 + c * 16);
-    }
-    uint32_t offA[2], offB[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        const uint32_t cb = (uint32_t)(((ks * 4 + fq) ^ fs) << 4);
-        offA[ks] = (uint32_t)((wm * 128 + frow) * 128) + cb;
-        offB[ks] = (uint32_t)(A_BYTES + (wn * 64 + frow) * 128) + cb;
-    }
-    const int nk = p.K / BK;
-
-    auto tile_rsrc = [&](int tile, __amdgpu_buffer_rsrc_t& rsA, __amdgpu_buffer_rsrc_t& rsB, int& m0, int& n0) {
-        const int tm = tile / ntn, tn = tile % ntn;
-        m0 = tm * BM; n0 = tn * BN;
-        const int64_t a_bytes = ((int64_t)(p.M - m0) * p.lda - (p.lda - p.K)) * 2;
-        const int64_t b_bytes = ((int64_t)(p.N - n0) * p.ldb - (p.ldb - p.K)) * 2;
-        rsA = make_rsrc(p.A + (int64_t)m0 * p.lda, (uint32_t)(a_bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : a_bytes));
-        rsB = make_rsrc(p.B + (int64_t)n0 * p.ldb, (uint32_t)(b_bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : b_bytes));
-    };
-    auto stage_load = [&](const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB, int stage, int kt) {
-        char* sA = smem + stage * STAGE_BYTES + wave * 4096;
-        char* sB = sA + A_BYTES;
-        const uint32_t koff = (uint32_t)kt * (BK * 2);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) lds_dma16(rsA, sA + i * 1024, voffA[i], koff);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) lds_dma16(rsB, sB + i * 1024, voffB[i], koff);
-    };
-
-    int tile = lane_pos;
-    __amdgpu_buffer_rsrc_t rsA, rsB;
-    int m0 = 0, n0 = 0;
-    if (tile < ntiles) {
-        tile_rsrc(tile, rsA, rsB, m0, n0);
-        stage_load(rsA, rsB, 0, 0);
-    }
-    while (tile < ntiles) {
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        __syncthreads();                       // K-step 0 of this tile has landed in stage 0
-        for (int kt = 0; kt < nk; ++kt) {
-            if (kt + 1 < nk && !(p.dbg & 4)) stage_load(rsA, rsB, (kt + 1) & 1, kt + 1);
-            const char* s = smem + (kt & 1) * STAGE_BYTES;
-            // Fragment pipeline: left alone, hipcc sinks every A-fragment read to just before its 4 MFMAs and waits
-            // lgkmcnt(0) there (minimal registers, LDS latency exposed per MFMA group).  Keep the A reads two groups
-            // ahead in a 3-deep register ring and pin the order with sched_barrier between groups.
-            bf16x8 b[2][4], aq[3];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) b[ks][j] = *(const bf16x8*)(s + offB[ks] + j * 2048);
-            aq[0] = *(const bf16x8*)(s + offA[0]);
-            aq[1] = *(const bf16x8*)(s + offA[0] + 2048);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const int ks = t >> 3, i = t & 7;
-                if (t + 2 < 16) aq[(t + 2) % 3] = *(const bf16x8*)(s + offA[(t + 2) >> 3] + ((t + 2) & 7) * 2048);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks][j], aq[t % 3], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (!(p.dbg & 8)) __syncthreads();
-        }
-        // both stages are free now: prefetch the next tile's first K-step into stage 0, stage the output through stage 1
-        const int cm0 = m0, cn0 = n0;
-        const int next = tile + G;
-        // the bias is fetched BEFORE the next tile's LDS-DMA is issued: vmcnt retires in issue order, so a bias load issued
-        // after the prefetch would make the epilogue wait for the prefetch to land before it can start
-        f32x4 bv[4];
-        load_bias<EPI>(p, cn0, wn, fq, bv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(bv[j]));      // ... and awaited here, while nothing else is in flight
-        if (next < ntiles) {
-            tile_rsrc(next, rsA, rsB, m0, n0);
-            stage_load(rsA, rsB, 0, 0);
-        }
-        staged_epilogue<EPI>(p, acc, smem + STAGE_BYTES, cm0, cn0, wm, wn, frow, fq, tid, bv);
-        tile = next;
     }
 }
 
@@ -349,7 +145,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 // ---------------------------------------------------------------------------------------------------------
 // Ping-pong persistent kernel (bf16-output epilogues, K >= 128).
 //
-// In the kernel above both waves of a SIMD do the same thing at the same time: at the top of every K-tile all eight
+// In the two-stage main loop (nt_core.h) both waves of a SIMD do the same thing at the same time: at the top of every K-tile all eight
 // waves issue their LDS-DMA burst (8 x ~150 cycles of issue each) and no MFMA runs; measured, the loop without its DMA
 // is 25-30 % faster.  Here the two wave groups of a workgroup (waves 0-3 = rows 0-127, waves 4-7 = rows 128-255; wave w and
 // w+4 share a SIMD) run the SAME instruction stream HALF A K-TILE APART, separated by the workgroup barrier: while one
@@ -705,7 +501,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(GemmNT p) {
         if (blockIdx.x < 8) tickets::put(p.tk_other + blockIdx.x, 0u);
     }
 
-    // DMA: wave fills row blocks wave*4 .. wave*4+3 (8 rows x 128 B) of the tile's A and B rows, as in the kernel above
+    // DMA: wave fills row blocks wave*4 .. wave*4+3 (8 rows x 128 B) of the tile's A and B rows, as in the two-stage main loop
     uint32_t voffA[2], voffB[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -1074,10 +870,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(GemmNT p) {
     if (dyn && tk_post == 0xA5A5A5A5u) tickets::post_g(mbox, tk_post);       // never true (tickets are < 2^30): keeps the store's data register
 }
 
-template <int EPI, int VAR, int ES = 2, int EMIT = 0>
-int32_t launch_pp_variant(const GemmNT& p_in, hipStream_t stream) {
-    // the ticket walk exists for the bf16 kernels (the e4m3 ones sit at the 256-register limit: BASELINE configs[4] keeps the static walk)
-    constexpr bool CAN_DYN = ES == 2;
+template <int EPI, int VAR, int ES, int EMIT>
+int32_t launch_pp(const GemmNT& p_in, bool ticket, hipStream_t stream) {
+    constexpr bool CAN_DYN = ES == 2;           // the ticket walk exists for the bf16 kernels only (nt_select.h)
     static DeviceOnce once;
     if (first_on_device(once)) {
         VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, VAR, ES, EMIT, false>,
@@ -1088,15 +883,9 @@ int32_t launch_pp_variant(const GemmNT& p_in, hipStream_t stream) {
         done_on_device(once);
     }
     GemmNT p = p_in;
-    const int64_t ntm = ceil_div(p.M, BM), ntn = ceil_div(p.N, BN);
-    const int64_t tiles = ntm * ntn;
-    int64_t grid = tiles < 256 ? (tiles + 7) / 8 * 8 : 256;
-    // ticket walk (common.h) when every XCD's queue holds more than the three rounds a workgroup takes statically: the shortest queue
-    // of the plain walk is the last one, of the column-grouped walk (VAR 8) the one of the last row quarter
-    const int64_t ppx = (ntm + 3) / 4;
-    const int64_t shortest = (VAR == 8 || VAR == 12) ? (ntm - 3 * ppx > 0 ? (ntm - 3 * ppx < ppx ? ntm - 3 * ppx : ppx) : 0) * (ntn / 2)
-                                      : (tiles >> 8) * 32 + ((tiles & 255) > 224 ? (tiles & 255) - 224 : 0);
-    if (CAN_DYN && grid == 256 && shortest > 128 && p.K >= 4 * BK && !(p.dbg & 4194304)) {      // bit 22 of VIPANT_GEMM_VARIANT: static walk (A/B)
+    const int64_t tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
+    const int64_t grid = tiles < 256 ? (tiles + 7) / 8 * 8 : 256;
+    if (CAN_DYN && ticket) {
         p.tk = vipant_ticket_block(stream, &p.tk_other);
         if (p.tk == nullptr) return VIPANT_EHIP;
         hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, VAR, ES, EMIT, CAN_DYN>), dim3((unsigned)grid), dim3(512), PP_LDS_BYTES, stream, p);
@@ -1104,47 +893,6 @@ int32_t launch_pp_variant(const GemmNT& p_in, hipStream_t stream) {
         return VIPANT_OK;
     }
     hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, VAR, ES, EMIT, false>), dim3((unsigned)grid), dim3(512), PP_LDS_BYTES, stream, p);
-    VIPANT_LAUNCH_CHECK();
-    return VIPANT_OK;
-}
-
-
-template <int EPI>
-int32_t launch_pp(const GemmNT& p, hipStream_t stream) {
-    // schedules of the ping-pong kernel: 0 = k-step intervals, 8 = the same on the column-grouped tile walk, 10 = DEEP, 12 = DEEP on the grouped walk
-    if (p.dbg & 131072) return launch_pp_variant<EPI, 10>(p, stream);      // bit 17: DEEP for every launch (A/B)
-    const bool groupable = ceil_div(p.N, BN) % 2 == 0 && ceil_div(p.M, BM) * ceil_div(p.N, BN) >= 256;
-    // the column-grouped walk is the default of the c_fc launch (853 vs 870-881 us, step -0.27 ms in-box; the QuickGELU' launch of
-    // the same shape does not move: profiles/r2_gemm_experiments.md section 9); bit 11 forces it everywhere, bit 12 turns it off
-    // round 5: the two K = 768 launches with 12 column tiles (c_fc + QuickGELU, QuickGELU') run the DEEP schedule ON the column-grouped
-    // walk (variant 12): half of the weight matrix per XCD stays in its L2 (the plain DEEP walk re-streams all of it every round:
-    // QuickGELU' fetched 1.93 GB for 0.75 GB of operands) and the look-ahead of DEEP is kept; 878.9 -> 870.2 us and 883.4 -> 872.2 us,
-    // alternating in one process, bit-identical (tools/grouped_walk_ab.py).  Bit 23 of VIPANT_GEMM_VARIANT: the round-4 choice (8 / 10).
-    if constexpr (EPI == VIPANT_EPI_QUICKGELU_D8 || EPI == VIPANT_EPI_DQUICKGELU_D8)
-        if (groupable && !(p.dbg & (8388608 | 4096 | 2048 | 262144))) return launch_pp_variant<EPI, 12>(p, stream);
-    // ... and plain launches with >= 8 column tiles (no shape of the ViT-B step: qkv has 9; the ViT-L qkv launch has 12)
-    if constexpr (EPI == VIPANT_EPI_BF16)
-        if (groupable && ceil_div(p.N, BN) >= 8 && !(p.dbg & (8388608 | 4096 | 2048 | 262144))) return launch_pp_variant<EPI, 12>(p, stream);
-    if (groupable && !(p.dbg & 4096) && (EPI == VIPANT_EPI_QUICKGELU_D8 || (p.dbg & 2048))) return launch_pp_variant<EPI, 8>(p, stream);
-    // the DEEP schedule (three barrier intervals of look-ahead for every operand piece, intervals by row halves): -2 ... -5 % on the
-    // launches with a long K or a wide N (qkv 608-624 -> 589-603 us, QuickGELU' 933-947 -> 916, dh2 627-634 -> 596-604), +3 % on the
-    // 768 x 768 ones, which keep the k-step schedule; bit 18 of VIPANT_GEMM_VARIANT: off
-    if (!(p.dbg & 262144) && (EPI == VIPANT_EPI_DQUICKGELU_D8 || (EPI == VIPANT_EPI_BF16 && (p.N >= 1024 || p.K >= 1024))))
-        return launch_pp_variant<EPI, 10>(p, stream);
-    return launch_pp_variant<EPI, 0>(p, stream);
-}
-
-template <int EPI>
-int32_t launch_persistent(const GemmNT& p, hipStream_t stream) {
-    static DeviceOnce once;
-    if (first_on_device(once)) {
-        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_persistent_kernel<EPI>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES));
-        done_on_device(once);
-    }
-    const int64_t tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
-    int64_t grid = tiles < 256 ? (tiles + 7) / 8 * 8 : 256;
-    hipLaunchKernelGGL(gemm_nt_persistent_kernel<EPI>, dim3((unsigned)grid), dim3(512), 2 * STAGE_BYTES, stream, p);
     VIPANT_LAUNCH_CHECK();
     return VIPANT_OK;
 }
@@ -1285,9 +1033,66 @@ int32_t launch_skinny_nw(const GemmNT& p, hipStream_t stream, int nb = 1) {
     VIPANT_LAUNCH_CHECK();
     return VIPANT_OK;
 }
-template <int EPI>
-int32_t launch_skinny(const GemmNT& p, hipStream_t stream) {
-    return launch_skinny_nw<EPI, 4>(p, stream);
+// ---------------------------------------------------------------------------------------------------------
+// From the selected instance (nt_select.h) to its template instance.  The lists below ARE the set of kernels this file holds: a
+// row more is a kernel more in the library.
+// ping-pong: (epilogue, schedule, ES, emit); every ES = 2 row exists on both walks (static stride, tickets)
+#define NT_PP_INSTANCES(X)                                      \
+    X(VIPANT_EPI_BF16, NT_KSTEP, 2, NT_EMIT_NONE)               \
+    X(VIPANT_EPI_BF16, NT_KSTEP_GROUPED, 2, NT_EMIT_NONE)       \
+    X(VIPANT_EPI_BF16, NT_DEEP, 2, NT_EMIT_NONE)                \
+    X(VIPANT_EPI_BF16, NT_DEEP_GROUPED, 2, NT_EMIT_NONE)        \
+    X(VIPANT_EPI_QUICKGELU, NT_KSTEP, 2, NT_EMIT_NONE)          \
+    X(VIPANT_EPI_QUICKGELU, NT_KSTEP_GROUPED, 2, NT_EMIT_NONE)  \
+    X(VIPANT_EPI_QUICKGELU, NT_DEEP, 2, NT_EMIT_NONE)           \
+    X(VIPANT_EPI_DQUICKGELU, NT_KSTEP, 2, NT_EMIT_NONE)         \
+    X(VIPANT_EPI_DQUICKGELU, NT_KSTEP_GROUPED, 2, NT_EMIT_NONE) \
+    X(VIPANT_EPI_DQUICKGELU, NT_DEEP, 2, NT_EMIT_NONE)          \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_KSTEP, 2, NT_EMIT_NONE)       \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_KSTEP_GROUPED, 2, NT_EMIT_NONE) \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_DEEP, 2, NT_EMIT_NONE)        \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_DEEP_GROUPED, 2, NT_EMIT_NONE) \
+    X(VIPANT_EPI_DQUICKGELU_D8, NT_KSTEP, 2, NT_EMIT_NONE)      \
+    X(VIPANT_EPI_DQUICKGELU_D8, NT_KSTEP_GROUPED, 2, NT_EMIT_NONE) \
+    X(VIPANT_EPI_DQUICKGELU_D8, NT_DEEP, 2, NT_EMIT_NONE)       \
+    X(VIPANT_EPI_DQUICKGELU_D8, NT_DEEP_GROUPED, 2, NT_EMIT_NONE) \
+    X(VIPANT_EPI_BF16, NT_KSTEP, 1, NT_EMIT_NONE)               \
+    X(VIPANT_EPI_BF16, NT_DEEP, 1, NT_EMIT_NONE)                \
+    X(VIPANT_EPI_BF16, NT_DEEP_GROUPED, 1, NT_EMIT_NONE)        \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_KSTEP, 1, NT_EMIT_NONE)       \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_KSTEP, 1, NT_EMIT_ALSO)       \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_KSTEP_GROUPED, 1, NT_EMIT_ALSO) \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_KSTEP, 1, NT_EMIT_ALONE)      \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_KSTEP, 1, NT_EMIT_WITH_CODES) \
+    X(VIPANT_EPI_QUICKGELU_D8, NT_KSTEP_GROUPED, 1, NT_EMIT_WITH_CODES) \
+    X(VIPANT_EPI_DQUICKGELU_D8, NT_KSTEP, 1, NT_EMIT_NONE)      \
+    X(VIPANT_EPI_DQUICKGELU_D8, NT_KSTEP, 1, NT_EMIT_ALSO)      \
+    X(VIPANT_EPI_DQUICKGELU_D8, NT_KSTEP_GROUPED, 1, NT_EMIT_ALSO) \
+    X(VIPANT_EPI_DQUICKGELU_D8, NT_KSTEP, 1, NT_EMIT_ALONE)     \
+    X(VIPANT_EPI_DQUICKGELU_D8, NT_KSTEP_GROUPED, 1, NT_EMIT_ALONE)
+// plain (one tile per workgroup) and few-rows kernels: by epilogue
+#define NT_PLAIN_INSTANCES(X) \
+    X(VIPANT_EPI_BF16) X(VIPANT_EPI_F32) X(VIPANT_EPI_RESIDUAL_F32) X(VIPANT_EPI_QUICKGELU) X(VIPANT_EPI_DQUICKGELU) X(VIPANT_EPI_SCALE_F32)
+#define NT_FEW_ROWS_INSTANCES(X) \
+    X(VIPANT_EPI_BF16) X(VIPANT_EPI_F32) X(VIPANT_EPI_RESIDUAL_F32) X(VIPANT_EPI_QUICKGELU_D8) X(VIPANT_EPI_DQUICKGELU_D8)
+
+static int32_t launch_instance(const NtInstance& k, const GemmNT& p, hipStream_t s) {
+    static_assert(NT_TILE == BM && NT_TILE == BN && NT_BK == BK, "nt_select.h counts tiles of another size");
+#define X(EPI, SCHED, ES, EMIT) \
+    if (k.family == NT_PINGPONG && k.epilogue == EPI && k.schedule == SCHED && k.es == ES && k.emit == EMIT) \
+        return launch_pp<EPI, SCHED, ES, EMIT>(p, k.ticket, s);
+    NT_PP_INSTANCES(X)
+#undef X
+#define X(EPI) if (k.family == NT_PLAIN && k.epilogue == EPI) return launch<EPI>(p, s);
+    NT_PLAIN_INSTANCES(X)
+#undef X
+#define X(EPI) if (k.family == NT_FEW_ROWS && k.epilogue == EPI) return launch_skinny_nw<EPI, 4>(p, s);
+    NT_FEW_ROWS_INSTANCES(X)
+#undef X
+    // a missing kernel is an error, never another kernel
+    vipant_set_error("gemm_nt: no kernel instance for family %d, epilogue %d, schedule %d, ES %d, emit %d", (int)k.family, k.epilogue,
+                     (int)k.schedule, k.es, (int)k.emit);
+    return VIPANT_EHIP;
 }
 
 extern "C" int32_t vipant_gemm_nt(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, void* C,
@@ -1303,63 +1108,28 @@ extern "C" int32_t vipant_gemm_nt(const uint16_t* A, int64_t lda, const uint16_t
                    "gemm_nt: operands must be 16-byte aligned");
     VIPANT_REQUIRE(256 * lda * 2 < (1ll << 31) && 256 * ldb * 2 < (1ll << 31), VIPANT_EBADSHAPE,
                    "gemm_nt: leading dimension too large");
-    const char* var = getenv("VIPANT_GEMM_VARIANT");       // read per call: tests and A/B scripts switch it inside one process
-    const int dbg = var ? atoi(var) : 0;
-    GemmNT p{(const bf16_t*)A, (const bf16_t*)B, C, bias, aux, lda, ldb, ldc, (int)M, (int)N, (int)K, alpha, dbg, nullptr, nullptr, 0, nullptr};
-    hipStream_t s = (hipStream_t)stream;
-    const bool staged = (N % 8 == 0) && (ldc % 8 == 0) && !(dbg & 2);
-    const bool pp = staged && K >= 128 && !(dbg & 16);
-    const bool few_rows = (epilogue & VIPANT_EPI_FEW_ROWS) != 0;
-    epilogue &= ~VIPANT_EPI_FEW_ROWS;
-    if (few_rows && !(dbg & 2097152)) {        // bit 21 of VIPANT_GEMM_VARIANT sends them through the 256 x 256 kernels again (A/B)
-        switch (epilogue) {
-            case VIPANT_EPI_BF16: return launch_skinny<VIPANT_EPI_BF16>(p, s);
-            case VIPANT_EPI_F32: return launch_skinny<VIPANT_EPI_F32>(p, s);
-            case VIPANT_EPI_RESIDUAL_F32:
-                VIPANT_REQUIRE(aux != nullptr, VIPANT_EBADSHAPE, "gemm_nt: residual epilogue needs aux");
-                return launch_skinny<VIPANT_EPI_RESIDUAL_F32>(p, s);
-            case VIPANT_EPI_QUICKGELU_D8:
-            case VIPANT_EPI_DQUICKGELU_D8:
-                VIPANT_REQUIRE(aux != nullptr && (uintptr_t)aux % 16 == 0, VIPANT_EBADSHAPE,
-                               "gemm_nt: the 8-bit QuickGELU' epilogues need aux (the code matrix), 16-byte aligned");
-                return epilogue == VIPANT_EPI_QUICKGELU_D8 ? launch_skinny<VIPANT_EPI_QUICKGELU_D8>(p, s)
-                                                            : launch_skinny<VIPANT_EPI_DQUICKGELU_D8>(p, s);
-            default:
-                vipant_set_error("gemm_nt: VIPANT_EPI_FEW_ROWS with epilogue %d (BF16, F32, RESIDUAL_F32 and the two _D8 epilogues only)", epilogue);
-                return VIPANT_EBADSHAPE;
-        }
-    }
-    switch (epilogue) {
-        case VIPANT_EPI_BF16:
-            if (pp) return launch_pp<VIPANT_EPI_BF16>(p, s);
-            return staged ? launch_persistent<VIPANT_EPI_BF16>(p, s) : launch<VIPANT_EPI_BF16>(p, s);
-        case VIPANT_EPI_F32: return launch<VIPANT_EPI_F32>(p, s);
-        case VIPANT_EPI_RESIDUAL_F32:
-            VIPANT_REQUIRE(aux != nullptr, VIPANT_EBADSHAPE, "gemm_nt: residual epilogue needs aux");
-            // one tile per workgroup: the only caller on the step's path is the last block on its read-out rows (`batch` rows, a handful
-            // of tiles), and the persistent form of this epilogue spilled 42 registers (the fp32 residual tile rides beside the
-            // accumulators); the instantiation is gone, so nothing on the step's path can pick it up again
-            return launch<VIPANT_EPI_RESIDUAL_F32>(p, s);
-        case VIPANT_EPI_QUICKGELU:
-            VIPANT_REQUIRE(aux != nullptr, VIPANT_EBADSHAPE, "gemm_nt: quickgelu epilogue needs aux (U out)");
-            if (pp) return launch_pp<VIPANT_EPI_QUICKGELU>(p, s);
-            return staged ? launch_persistent<VIPANT_EPI_QUICKGELU>(p, s) : launch<VIPANT_EPI_QUICKGELU>(p, s);
-        case VIPANT_EPI_DQUICKGELU:
-            VIPANT_REQUIRE(aux != nullptr, VIPANT_EBADSHAPE, "gemm_nt: dquickgelu epilogue needs aux (U in)");
-            if (pp) return launch_pp<VIPANT_EPI_DQUICKGELU>(p, s);
-            return staged ? launch_persistent<VIPANT_EPI_DQUICKGELU>(p, s) : launch<VIPANT_EPI_DQUICKGELU>(p, s);
-        case VIPANT_EPI_QUICKGELU_D8:
-        case VIPANT_EPI_DQUICKGELU_D8:
-            VIPANT_REQUIRE(aux != nullptr, VIPANT_EBADSHAPE, "gemm_nt: the 8-bit QuickGELU' epilogues need aux (the code matrix)");
-            VIPANT_REQUIRE(staged && K >= 128 && (uintptr_t)aux % 16 == 0, VIPANT_EBADSHAPE,
+    const int sw = vipant_switches();
+    GemmNT p{(const bf16_t*)A, (const bf16_t*)B, C, bias, aux, lda, ldb, ldc, (int)M, (int)N, (int)K, alpha, sw, nullptr, nullptr, 0, nullptr};
+    const NtLaunch l{M, N, K, ldc, epilogue & ~VIPANT_EPI_FEW_ROWS, (epilogue & VIPANT_EPI_FEW_ROWS) != 0, C == nullptr, aux == nullptr, true,
+                     (uintptr_t)aux % 16 != 0, sw};
+    NtInstance k;
+    switch (nt_select_bf16(l, &k)) {
+        case NT_ACCEPT: break;
+        case NT_RESIDUAL_NEEDS_AUX: VIPANT_REQUIRE(false, VIPANT_EBADSHAPE, "gemm_nt: residual epilogue needs aux");
+        case NT_QUICKGELU_NEEDS_AUX: VIPANT_REQUIRE(false, VIPANT_EBADSHAPE, "gemm_nt: quickgelu epilogue needs aux (U out)");
+        case NT_DQUICKGELU_NEEDS_AUX: VIPANT_REQUIRE(false, VIPANT_EBADSHAPE, "gemm_nt: dquickgelu epilogue needs aux (U in)");
+        case NT_D8_NEEDS_AUX: VIPANT_REQUIRE(false, VIPANT_EBADSHAPE, "gemm_nt: the 8-bit QuickGELU' epilogues need aux (the code matrix)");
+        case NT_D8_NEEDS_ALIGNED_AUX:
+            VIPANT_REQUIRE(false, VIPANT_EBADSHAPE, "gemm_nt: the 8-bit QuickGELU' epilogues need aux (the code matrix), 16-byte aligned");
+        case NT_D8_NEEDS_STAGED:
+            VIPANT_REQUIRE(false, VIPANT_EBADSHAPE,
                            "gemm_nt: the 8-bit QuickGELU' epilogues need N %% 8 == 0, ldc %% 8 == 0, K >= 128 and a 16-byte aligned aux");
-            return epilogue == VIPANT_EPI_QUICKGELU_D8 ? launch_pp<VIPANT_EPI_QUICKGELU_D8>(p, s)
-                                                        : launch_pp<VIPANT_EPI_DQUICKGELU_D8>(p, s);
-        case VIPANT_EPI_SCALE_F32: return launch<VIPANT_EPI_SCALE_F32>(p, s);
-        default:
-            vipant_set_error("gemm_nt: unknown epilogue %d", epilogue);
-            return VIPANT_EBADSHAPE;
+        case NT_FEW_ROWS_EPILOGUE:
+            VIPANT_REQUIRE(false, VIPANT_EBADSHAPE,
+                           "gemm_nt: VIPANT_EPI_FEW_ROWS with epilogue %d (BF16, F32, RESIDUAL_F32 and the two _D8 epilogues only)", l.epilogue);
+        default: VIPANT_REQUIRE(false, VIPANT_EBADSHAPE, "gemm_nt: unknown epilogue %d", l.epilogue);
     }
+    return launch_instance(k, p, (hipStream_t)stream);
 }
 
 // H independent small products in one launch of the few-rows kernel: the per-head contractions of the folded last block
@@ -1418,54 +1188,21 @@ extern "C" int32_t vipant_gemm_nt_e4m3(const uint8_t* A, int64_t lda, const uint
     VIPANT_REQUIRE(C != nullptr || (cq != nullptr && (epilogue == VIPANT_EPI_QUICKGELU_D8 || epilogue == VIPANT_EPI_DQUICKGELU_D8)), VIPANT_EBADSHAPE,
                    "gemm_nt_e4m3: C may be NULL only when one of the QuickGELU epilogues leaves the e4m3 form in its place");
     VIPANT_REQUIRE(256 * lda < (1ll << 31) && 256 * ldb < (1ll << 31), VIPANT_EBADSHAPE, "gemm_nt_e4m3: leading dimension too large");
-    const char* var = getenv("VIPANT_GEMM_VARIANT");       // read per call, as in vipant_gemm_nt
-    const int fp8_dbg = var ? atoi(var) : 0;
-    GemmNT p{(const bf16_t*)A, (const bf16_t*)B, C, bias, aux, lda, ldb, ldc, (int)M, (int)N, (int)K, 1.0f, fp8_dbg & (4194304 | (1 << 27) | (1 << 28)), sa, sb, 0, nullptr};
+    const int sw = vipant_switches();
+    // (the device sees only the bits its e4m3 kernels read)
+    GemmNT p{(const bf16_t*)A, (const bf16_t*)B, C, bias, aux, lda, ldb, ldc, (int)M, (int)N, (int)K, 1.0f,
+             sw & (VIPANT_SW_STATIC_WALK | VIPANT_SW_E4M3_GROUPED_UNPAIRED | VIPANT_SW_E4M3_PLAIN_UNPAIRED), sa, sb, 0, nullptr};
     p.cq = cq; p.cqs = cq_scale;
-    hipStream_t s = (hipStream_t)stream;
-    switch (epilogue) {
-        case VIPANT_EPI_BF16:
-            // the deep look-ahead schedule (VAR 10): -2..-4 % at K >= 3072, neutral at K <= 1024; bit 15 of VIPANT_GEMM_VARIANT: off
-            // wide outputs (>= 8 column tiles, an even number): DEEP on the column-grouped walk -- the ViT-L qkv launch (N = 3072, K = 1024)
-            // 1172 -> 1133 us, bit-identical; at N = 1024 (four column tiles) it gains nothing or loses.  Bit 26: off.
-            if (!(fp8_dbg & (67108864 | 32768)) && ceil_div(M, BM) * ceil_div(N, BN) >= 256 && ceil_div(N, BN) % 2 == 0 && ceil_div(N, BN) >= 8)
-                return launch_pp_variant<VIPANT_EPI_BF16, 12, 1>(p, s);
-            if (!(fp8_dbg & 32768)) return launch_pp_variant<VIPANT_EPI_BF16, 10, 1>(p, s);
-            return launch_pp_variant<VIPANT_EPI_BF16, 0, 1>(p, s);
-        case VIPANT_EPI_QUICKGELU_D8:
-        case VIPANT_EPI_DQUICKGELU_D8:
-            VIPANT_REQUIRE((aux != nullptr || (C == nullptr && cq != nullptr)) && (uintptr_t)aux % 16 == 0, VIPANT_EBADSHAPE,
-                           "gemm_nt_e4m3: the 8-bit QuickGELU' epilogues need a 16-byte aligned aux (the code matrix)");
-            if (cq != nullptr && epilogue == VIPANT_EPI_QUICKGELU_D8 && C != nullptr && aux == nullptr) {
-                vipant_set_error("gemm_nt_e4m3: C without aux (the code matrix)");
-                return VIPANT_EBADSHAPE;
-            }
-            if (cq != nullptr && epilogue == VIPANT_EPI_QUICKGELU_D8 && C == nullptr && aux == nullptr)
-                return launch_pp_variant<VIPANT_EPI_QUICKGELU_D8, 0, 1, 2>(p, s);           // the e4m3 form alone
-            if (cq != nullptr && epilogue == VIPANT_EPI_QUICKGELU_D8 && C == nullptr) {      // the e4m3 form + the codes
-                if (ceil_div(M, BM) * ceil_div(N, BN) >= 256 && ceil_div(N, BN) % 2 == 0 && !(fp8_dbg & 33554432))
-                    return launch_pp_variant<VIPANT_EPI_QUICKGELU_D8, 8, 1, 3>(p, s);
-                return launch_pp_variant<VIPANT_EPI_QUICKGELU_D8, 0, 1, 3>(p, s);
-            }
-            if (cq != nullptr && epilogue == VIPANT_EPI_DQUICKGELU_D8 && C == nullptr) {     // QuickGELU': the e4m3 form alone
-                if (ceil_div(M, BM) * ceil_div(N, BN) >= 256 && ceil_div(N, BN) % 2 == 0 && !(fp8_dbg & 33554432))
-                    return launch_pp_variant<VIPANT_EPI_DQUICKGELU_D8, 8, 1, 2>(p, s);
-                return launch_pp_variant<VIPANT_EPI_DQUICKGELU_D8, 0, 1, 2>(p, s);
-            }
-            if (cq != nullptr) {
-                // the column-grouped walk (k-step schedule; half of the weight bytes per XCD): 2186 -> 2149 us and 2329 -> 2305 us at the
-                // ViT-L shape, bit-identical; DEEP on the grouped walk gains nothing here.  Bit 25 of VIPANT_GEMM_VARIANT: the plain walk.
-                const bool groupable = ceil_div(M, BM) * ceil_div(N, BN) >= 256 && ceil_div(N, BN) % 2 == 0;
-                if (groupable && !(fp8_dbg & 33554432))
-                    return epilogue == VIPANT_EPI_QUICKGELU_D8 ? launch_pp_variant<VIPANT_EPI_QUICKGELU_D8, 8, 1, 1>(p, s)
-                                                                : launch_pp_variant<VIPANT_EPI_DQUICKGELU_D8, 8, 1, 1>(p, s);
-                return epilogue == VIPANT_EPI_QUICKGELU_D8 ? launch_pp_variant<VIPANT_EPI_QUICKGELU_D8, 0, 1, 1>(p, s)
-                                                            : launch_pp_variant<VIPANT_EPI_DQUICKGELU_D8, 0, 1, 1>(p, s);
-            }
-            return epilogue == VIPANT_EPI_QUICKGELU_D8 ? launch_pp_variant<VIPANT_EPI_QUICKGELU_D8, 0, 1>(p, s)
-                                                        : launch_pp_variant<VIPANT_EPI_DQUICKGELU_D8, 0, 1>(p, s);
+    const NtLaunch l{M, N, K, ldc, epilogue, false, C == nullptr, aux == nullptr, cq == nullptr, (uintptr_t)aux % 16 != 0, sw};
+    NtInstance k;
+    switch (nt_select_e4m3(l, &k)) {
+        case NT_ACCEPT: break;
+        case NT_D8_NEEDS_ALIGNED_AUX:
+            VIPANT_REQUIRE(false, VIPANT_EBADSHAPE, "gemm_nt_e4m3: the 8-bit QuickGELU' epilogues need a 16-byte aligned aux (the code matrix)");
+        case NT_E4M3_C_WITHOUT_AUX: VIPANT_REQUIRE(false, VIPANT_EBADSHAPE, "gemm_nt_e4m3: C without aux (the code matrix)");
         default:
-            vipant_set_error("gemm_nt_e4m3: epilogue %d is not built for e4m3 operands (bf16 and the two 8-bit QuickGELU' ones are)", epilogue);
-            return VIPANT_EBADSHAPE;
+            VIPANT_REQUIRE(false, VIPANT_EBADSHAPE,
+                           "gemm_nt_e4m3: epilogue %d is not built for e4m3 operands (bf16 and the two 8-bit QuickGELU' ones are)", epilogue);
     }
+    return launch_instance(k, p, (hipStream_t)stream);
 }

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace {
 
@@ -851,7 +852,7 @@ extern "C" int32_t vipant_gemm_tn(const uint16_t* A, int64_t lda, const uint16_t
                                            2 * STAGE_BYTES));
         VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            PP_LDS_BYTES));
-        variant = getenv("VIPANT_GEMM_VARIANT") ? atoi(getenv("VIPANT_GEMM_VARIANT")) : 0;     // bit 16: the two-stage kernel
+        variant = vipant_switches();       // (read once per device here) VIPANT_SW_TWO_STAGE: the two-stage kernel
         done_on_device(once);
     }
     hipStream_t s = (hipStream_t)stream;
@@ -860,7 +861,7 @@ extern "C" int32_t vipant_gemm_tn(const uint16_t* A, int64_t lda, const uint16_t
     float* cs_part = a_colsum != nullptr ? (float*)((char*)workspace + slab_bytes) : nullptr;
     GemmTN p{(const bf16_t*)A, (const bf16_t*)B, direct ? C : (float*)workspace, lda, ldb, direct ? ldc : TQ,
              (int)M, (int)P, (int)Q, splits, per, direct, cs_part};
-    if (variant & 16) hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)(tiles * splits)), dim3(512), 2 * STAGE_BYTES, s, p);
+    if (variant & VIPANT_SW_TWO_STAGE) hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)(tiles * splits)), dim3(512), 2 * STAGE_BYTES, s, p);
     else hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3((unsigned)(tiles * splits)), dim3(512), PP_LDS_BYTES, s, p);
     VIPANT_LAUNCH_CHECK();
     const int cs_parts = (int)(splits * ceil_div(Q, TQ)), cs_stride = (int)(ceil_div(P, TP) * TP);
