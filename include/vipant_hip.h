@@ -257,9 +257,15 @@ int32_t vipant_gemm_tn_e4m3(const uint8_t* A, int64_t lda, const uint8_t* sa, co
  * the instruction's block-scale operands).  A [M, K] e4m3: an activation, sa = its BLOCK scales (vipant_quant_e4m3_mx layout); B [N, K]
  * e4m3: a weight matrix, sb = one scale per row (vipant_quant_e4m3_rows).  Epilogues: VIPANT_EPI_BF16, VIPANT_EPI_QUICKGELU_D8,
  * VIPANT_EPI_DQUICKGELU_D8, meaning as in vipant_gemm_nt.  cq / cq_scale (both or neither; the two QuickGELU epilogues, N % 128 == 0):
- * the epilogue ALSO leaves the e4m3 form of its bf16 result, bytes [M, N] + block scales -- vipant_quant_e4m3_mx of C bit for bit --
- * i.e. the next contraction's A operand quantised where it is produced; with cq set and VIPANT_EPI_QUICKGELU_D8, C and aux may be
- * NULL (only the e4m3 form is wanted).  K % 128 == 0, K >= 256, N % 8 == 0, leading dimensions (in elements = bytes) multiples of 16. */
+ * the epilogue ALSO leaves the e4m3 form of its bf16 result, bytes [M, N] (row length N) + block scales in the MX layout, in the
+ * BLOCK-UNIFORM form of vipant_quant_e4m3_mx32: one scale per aligned block of 32 rows x 32 columns.  The scale is taken from a bound
+ * on the block (the largest |acc + bias| of the wave that holds it, times 1.01, resp. 1.11 for QuickGELU'), not from the block's exact
+ * maximum: it is never below what the block's largest element needs (nothing saturates) and at most two binades above it, so the
+ * scales are NOT those of vipant_quant_e4m3_mx32 bit for bit; the bytes are C / 2^e rounded to e4m3 under the scale written.  Bytes
+ * and scale bytes are written for rows below M only (in a last 32-row block that straddles M, the rows beyond M keep whatever
+ * cq_scale held).  It is the next
+ * contraction's A operand quantised where it is produced; with cq set, C may be NULL (only the e4m3 form is wanted), and with
+ * VIPANT_EPI_QUICKGELU_D8 aux too (no codes).  K % 128 == 0, K >= 256, N % 8 == 0, leading dimensions (in elements = bytes) multiples of 16. */
 int32_t vipant_gemm_nt_e4m3(const uint8_t* A, int64_t lda, const uint8_t* sa, const uint8_t* B, int64_t ldb, const uint8_t* sb,
                             void* C, int64_t ldc, const float* bias, void* aux, uint8_t* cq, uint8_t* cq_scale, int64_t M, int64_t N,
                             int64_t K, int32_t epilogue, void* stream);

@@ -5,6 +5,8 @@ fp32 matmul of the SAME dequantised operands within bf16 output rounding, and th
 import pytest
 import torch
 
+from mx_emul import check_block_uniform_form, dequant, dequant_mx, emulate_quant_mx32, mx_scales
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -32,10 +34,6 @@ def emulate_quant(x_bf16):
     return q, (e + 127).to(torch.uint8)
 
 
-def dequant(q_u8, s_u8):
-    return q_u8.view(torch.float8_e4m3fn).float() * torch.exp2(s_u8.float() - 127)[:, None]
-
-
 def emulate_quant_mx(x_bf16):
     """the block format of the ACTIVATION operands (round 5): per 32 consecutive elements of a row, e = the smallest exponent with
     amax / 2^e <= 448; q = rne(x / 2^e) in OCP e4m3.  Returns (q [M, K] float8, scale bytes [M, K / 32])."""
@@ -47,17 +45,6 @@ def emulate_quant_mx(x_bf16):
     e = torch.where(amax > 0, e, torch.full_like(e, -127)).clamp(-127, 127)      # an all-zero block: the smallest scale, byte 0 (round 6)
     q = (x * torch.exp2(-e)[:, :, None]).to(torch.float8_e4m3fn).view(M, K)
     return q, (e + 127).to(torch.uint8)
-
-
-def mx_scales(ops, s_tiled, M, K):
-    """the library's scale array (MX layout) -> scale bytes [M, K / 32]"""
-    return s_tiled[ops.mx_scale_index(M, K, s_tiled.device)]
-
-
-def dequant_mx(ops, q_u8, s_tiled):
-    M, K = q_u8.shape
-    sc = torch.exp2(mx_scales(ops, s_tiled, M, K).float() - 127)
-    return (q_u8.view(torch.float8_e4m3fn).float().view(M, K // 32, 32) * sc[:, :, None]).view(M, K)
 
 
 @pytest.mark.parametrize("M,K", [(5, 256), (300, 1024), (1031, 768), (64, 4096), (129, 3072), (128, 128)])
@@ -78,22 +65,6 @@ def test_block_quantiser_matches_the_stated_format(ops, M, K):
     blk = x.float().view(M, K // 32, 32)
     rel = (back.view(M, K // 32, 32) - blk).abs().amax(dim=2) / blk.abs().amax(dim=2).clamp_min(1e-30)
     assert float(rel.max()) <= 2 ** -4 + 1e-6                                              # half an ulp of the BLOCK maximum
-
-
-def emulate_quant_mx32(x_bf16):
-    """block-uniform format (round 6): one exponent per aligned block of 32 rows x 32 columns; (q float8 [M, K], scale bytes [M, K / 32])."""
-    M, K = x_bf16.shape
-    Mp = (M + 31) // 32 * 32
-    x = torch.zeros(Mp, K, dtype=torch.float32, device=x_bf16.device)
-    x[:M] = x_bf16.float()
-    blk = x.view(Mp // 32, 32, K // 32, 32)
-    amax = blk.abs().amax(dim=(1, 3))
-    e = torch.floor(torch.log2(amax.clamp_min(1e-38))) - 8
-    e = torch.where(amax * torch.exp2(-e) > 448, e + 1, e)
-    e = torch.where(amax > 0, e, torch.full_like(e, -127)).clamp(-127, 127)
-    q = (blk * torch.exp2(-e)[:, None, :, None]).to(torch.float8_e4m3fn).view(Mp, K)[:M]
-    s = (e + 127).to(torch.uint8)[:, None, :].expand(Mp // 32, 32, K // 32).reshape(Mp, K // 32)[:M]
-    return q, s
 
 
 @pytest.mark.parametrize("M,K", [(5, 256), (300, 1024), (1031, 768), (64, 4096), (129, 3072), (128, 128), (248, 2304)])
@@ -221,28 +192,6 @@ def test_e4m3_contraction_is_exact_on_its_operands(ops, M, N, K):
     full = a.double() @ b.double().t() + bias.double()
     dist = ((c.double() - full).norm(dim=1) / full.norm(dim=1)).median()
     assert float(dist) < 6e-2, float(dist)            # e4m3 x e4m3 on gaussian rows: ~2^-4 / sqrt(3) per factor, observed ~3.7e-2
-
-
-def check_block_uniform_form(ops, em, ref_bf16, slack):
-    """(bytes, scales) left by a producer for the bf16 matrix `ref_bf16`: scales uniform over aligned 32 x 32 blocks, never below
-    what the block's largest element needs (nothing saturates) and at most `slack` binades above it (the producers take the scale
-    from a bound they have in registers, not from the exact maximum), and the bytes exactly ref / 2^e rounded to e4m3."""
-    M, N = ref_bf16.shape
-    s = mx_scales(ops, em[1], M, N).int()
-    _, s_min = emulate_quant_mx32(ref_bf16)
-    Mp = (M + 31) // 32 * 32
-    pad = torch.zeros(Mp, N // 32, dtype=torch.int32, device=s.device); pad[:M] = s
-    pad[M:] = pad[(M - 1) // 32 * 32]                                  # rows beyond M: whatever the block has
-    blk = pad.view(Mp // 32, 32, N // 32)
-    assert torch.equal(blk.amax(dim=1), blk.amin(dim=1))                # one scale per block
-    nz = s_min.int() > 0
-    assert bool((s[nz] >= s_min.int()[nz]).all()) and bool((s[nz] <= s_min.int()[nz] + slack).all()), \
-        (int((s - s_min.int())[nz].min()), int((s - s_min.int())[nz].max()))
-    sc = torch.exp2(s.float() - 127)[:, :, None].expand(M, N // 32, 32).reshape(M, N)
-    want = (ref_bf16.float() / sc).to(torch.float8_e4m3fn).view(torch.uint8)
-    zero_blk = (~nz)[:, :, None].expand(M, N // 32, 32).reshape(M, N)
-    assert torch.equal(em[0][~zero_blk], want[~zero_blk])
-    print(f"block-uniform emit: scale - minimal scale: mean {float((s - s_min.int())[nz].float().mean()):.3f} binades")
 
 
 def test_e4m3_quickgelu_epilogues(ops):

@@ -1,6 +1,7 @@
 """Per-kernel parity on the MI355X: every C-ABI entry point against a plain fp32/fp64 PyTorch
 restatement of the same op on identical (bf16-rounded) inputs.  Tolerances are written next to each check:
-bf16 outputs carry 2^-9 relative rounding, fp32-accumulated contractions of K terms ~1e-3 of the output scale.
+bf16 outputs carry one rounding of unit roundoff 2^-8 (eight significant bits: at most 2^-9 of the next power of two above the
+value, up to 2^-8 of the value itself), fp32-accumulated contractions of K terms ~1e-3 of the output scale.
 """
 import math
 
