@@ -39,8 +39,8 @@ against (|A|^T |B|)[p, q].  Depth of a_colsum[p], from the column-sum code of tn
 against sum |a|.  The worst error / bound ratio of every case is printed, and written to the file VIPANT_TN_PARITY_LOG names if it is
 set (profiles/tn_parity_observed.txt is one such run), so that a later change can tighten the bound with evidence.
 
-Out of scope: the round-1 two-stage kernel behind VIPANT_SW_TWO_STAGE.  The switch is read once per device, so it would need a child
-process of its own, and the kernel does not ship."""
+Nothing of gemm_tn.hip is out of scope: the file holds the three ping-pong kernels and the reductions these tests reach (the round-1
+two-stage kernel that VIPANT_SW_TWO_STAGE used to select was removed), and the plan they follow is csrc/tn_plan.h."""
 import os
 
 import pytest

@@ -1,7 +1,11 @@
 """The CPU half of tests/test_gemm_tn_gpu.py: the Python restatement of the TN contraction's split plans (tests/tn_plan.py) agrees
-with the library's three workspace queries on every listed and a few hundred pseudo-random shapes, with VIPANT_TN_SPLIT unset, 2 and
-4 -- `splits` follows from the byte count -- and the GPU tests' case lists keep every property they were chosen for."""
+with vipant_amd/csrc/tn_plan.h in every field (the header is compiled alone by the host compiler into tests/tn_plan_main.cpp) and with
+the library's three workspace queries -- the check that the library uses the header -- on every listed and a few hundred
+pseudo-random shapes, and the GPU tests' case lists keep every property they were chosen for."""
+import os
 import random
+import shutil
+import subprocess
 
 import pytest
 
@@ -43,6 +47,33 @@ def test_restated_plans_agree_with_the_workspace_queries(query, monkeypatch, env
             assert 1 <= l.last <= l.per and (l.splits - 1) * l.per + l.last == l.nk and l.parts == l.splits * l.ntq
             seen.add((name, l.splits > 1, l.last < l.per))
     assert len(seen) >= 8, seen          # every query met single and several splits, with and without a short last one
+
+
+def test_restated_plans_agree_with_the_header_in_every_field(tmp_path):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "tn_plan_main")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-o", exe, os.path.join(root, "tests", "tn_plan_main.cpp")], check=True)
+    asked, want = [], []
+    for M, P, Q in shapes():
+        for factor in (1, 2, 4, 8):
+            for acc in (0, 1):
+                for kind, l in (("bf16", T.plan(M, P, Q, bool(acc), factor)), ("e4m3", T.plan8(M, P, Q, bool(acc), factor)), ("pair", T.plan_pair(M, P, Q))):
+                    asked.append(f"{kind} {M} {P} {Q} {factor} {acc}")
+                    want.append(f"ntp={l.ntp} ntq={l.ntq} tiles={l.tiles} nk={l.nk} splits={l.splits} per={l.per} direct={int(l.direct)} "
+                                f"slab_bytes={l.slab_bytes} colsum_bytes={l.colsum_bytes} workspace_bytes={l.ws_bytes} "
+                                f"reduce_blocks={l.reduce_blocks} cs_parts={l.parts} cs_stride={l.cs_stride}")
+    got = subprocess.run([exe], input="\n".join(asked) + "\n", stdout=subprocess.PIPE, text=True, check=True).stdout.splitlines()
+    assert len(got) == len(asked) >= 24 * 400
+    wrong = [f"{a}: header `{g}`, tests/tn_plan.py `{w}`" for a, g, w in zip(asked, got, want) if g != w]
+    assert not wrong, "\n".join(wrong[:20])
+    # both sides of what the fields decide: the two reduce-grid caps, direct and slab launches, factors that move the plan and that do not
+    plans = [dict(f.split("=") for f in g.split()) for g in got]
+    capped = {(a.split()[0], int(p["reduce_blocks"]) == (1024 if a.startswith("pair") else 2048)) for a, p in zip(asked, plans)}
+    assert capped == {(k, c) for k in ("bf16", "e4m3", "pair") for c in (False, True)}
+    assert {(a.split()[0], p["direct"]) for a, p in zip(asked, plans)} == {(k, d) for k in ("bf16", "e4m3", "pair") for d in "01"}
+    assert all(p["colsum_bytes"] == "0" for a, p in zip(asked, plans) if a.startswith("pair"))
 
 
 def test_split_factor_is_atoi_clamped_to_1_8(monkeypatch):

@@ -1,8 +1,9 @@
-"""The split plans of the TN contraction (vipant_amd/csrc/gemm_tn.hip: plan(), plan8(), plan_tiles(), split_factor()) restated in
-plain Python, and the case lists of tests/test_gemm_tn_gpu.py with the properties those lists must keep.
+"""The split plans of the TN contraction (vipant_amd/csrc/tn_plan.h: tn_plan(), tn_split_factor()) restated in plain Python, and
+the case lists of tests/test_gemm_tn_gpu.py with the properties those lists must keep.
 
-Nothing here touches a GPU.  tests/test_tn_plan_cpu.py ties the restatement to the library through the three workspace queries
-(`splits` follows from the byte count) and runs check_coverage() on the lists, so neither can drift unnoticed."""
+Nothing here touches a GPU.  tests/test_tn_plan_cpu.py ties the restatement to the header field by field (tests/tn_plan_main.cpp,
+built by the host compiler) and to the library through the three workspace queries, and runs check_coverage() on the lists, so none
+of them can drift unnoticed."""
 import os
 from collections import namedtuple
 
@@ -33,7 +34,7 @@ def split_factor(env=None):
     return 1 if k < 1 else (8 if k > 8 else k)
 
 
-Launch = namedtuple("Launch", "M P Q bk tiles ntp ntq nk splits per last direct parts mtail ws_bytes")
+Launch = namedtuple("Launch", "M P Q bk tiles ntp ntq nk splits per last direct parts mtail ws_bytes slab_bytes colsum_bytes reduce_blocks cs_stride")
 
 
 def _launch(M, P, Q, bk, tiles_in_plan, factor, accumulate, pair):
@@ -45,27 +46,27 @@ def _launch(M, P, Q, bk, tiles_in_plan, factor, accumulate, pair):
     per = ceil_div(nk, s)
     splits = ceil_div(nk, per)
     last = nk - (splits - 1) * per
-    if pair:
-        ws = 2 * splits * tiles * SLAB_TILE_BYTES
-    else:
-        ws = splits * tiles * SLAB_TILE_BYTES + splits * ntq * ntp * TP * 4
-    return Launch(M, P, Q, bk, tiles, ntp, ntq, nk, splits, per, last, splits == 1 and not accumulate, splits * ntq, M % bk, ws)
+    slab = splits * tiles * SLAB_TILE_BYTES                                     # per problem; the workspace holds the slab(s) first,
+    colsum = 0 if pair else splits * ntq * ntp * TP * 4                         # then the column-sum partials
+    blocks = min(ceil_div(tiles * TP * TQ // 4, 256), REDUCE_GRID_CAP_PAIR if pair else REDUCE_GRID_CAP)
+    return Launch(M, P, Q, bk, tiles, ntp, ntq, nk, splits, per, last, splits == 1 and not accumulate, splits * ntq, M % bk,
+                  (2 if pair else 1) * slab + colsum, slab, colsum, blocks, ntp * TP)
 
 
 def plan(M, P, Q, accumulate=False, factor=None):
-    """vipant_gemm_tn: plan().  `factor`: the VIPANT_TN_SPLIT factor (None: from the environment)."""
+    """vipant_gemm_tn.  `factor`: the VIPANT_TN_SPLIT factor (None: from the environment)."""
     tiles = ceil_div(P, TP) * ceil_div(Q, TQ)
     return _launch(M, P, Q, BK, tiles, split_factor() if factor is None else factor, accumulate, False)
 
 
 def plan8(M, P, Q, accumulate=False, factor=None):
-    """vipant_gemm_tn_e4m3: plan8(), K-tiles of 128 tokens."""
+    """vipant_gemm_tn_e4m3: K-tiles of 128 tokens."""
     tiles = ceil_div(P, TP) * ceil_div(Q, TQ)
     return _launch(M, P, Q, BK8, tiles, split_factor() if factor is None else factor, accumulate, False)
 
 
 def plan_pair(M, P, Q):
-    """vipant_gemm_tn_pair: plan_tiles() on twice the tile count; VIPANT_TN_SPLIT does not apply, nothing accumulates."""
+    """vipant_gemm_tn_pair: twice the tile count enters the plan; VIPANT_TN_SPLIT does not apply, nothing accumulates."""
     tiles = ceil_div(P, TP) * ceil_div(Q, TQ)
     return _launch(M, P, Q, BK, 2 * tiles, 1, False, True)
 

@@ -8,203 +8,34 @@
 // (on the DMA source address and on the read address) so the 32 lanes of a half-wave hit all 64 banks.
 // 256x256 output tile per 512-thread workgroup; the M range is split over workgroups to fill 256 CUs and
 // the fp32 partial tiles are summed by a second deterministic pass (no float atomics).
+// The split plan (how many workgroups per tile, the workspace, the reduction grids) lives in tn_plan.h.
 #include <stdlib.h>
 
+#include <initializer_list>
+
 #include "common.h"
-#include "switches.h"
+#include "tn_plan.h"
 
 namespace {
 
-constexpr int TP = 256, TQ = 256, BK = 64;
-constexpr int OP_BYTES = BK * TP * 2;       // 32 KiB per operand tile
-constexpr int STAGE_BYTES = 2 * OP_BYTES;   // 64 KiB
+constexpr int TP = (int)TN_TILE, TQ = (int)TN_TILE, BK = TN_BK, BK8 = TN_BK8;
 
-struct GemmTN {
-    const bf16_t* A; const bf16_t* B; float* out;  // out: slab base (splits > 1) or C
-    int64_t lda, ldb, ldo;
+// what the kernels of both operand formats are told about a problem
+struct TnProblem {
+    float* out;                  // slab base (splits > 1 or accumulate) or C
+    int64_t lda, ldb, ldo;       // lda / ldb in elements: for e4m3 also the bytes per token row and the row length of the scale layouts
     int M, P, Q;
-    int splits, kt_per_split;
-    int direct;   // 1: write straight into C (single split, no accumulate)
-    float* colsum;   // optional [splits * ntq][ntp*256]: partial column sums of A (bias gradient of the same Linear)
+    int splits, kt_per_split;    // in K-tiles of BK (bf16) / BK8 (e4m3) tokens
+    int direct;                  // 1: write straight into C (single split, no accumulate)
+    float* colsum;               // optional [splits * ntq][ntp * 256]: partial column sums of A (the bias gradient of the same Linear)
 };
+struct GemmTN : TnProblem { const bf16_t* A; const bf16_t* B; };
 
 __device__ __forceinline__ int tn_swz(int m) { return ((m & 3) | (((m >> 3) & 1) << 2)) << 1; }
 
-__global__ __launch_bounds__(512, 2) void gemm_tn_kernel(GemmTN p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wp = wave >> 2, wq = wave & 3;
-
-    const int ntq = (p.Q + TQ - 1) / TQ, ntp = (p.P + TP - 1) / TP;
-    const int ntiles = ntp * ntq;
-    const int bid = xcd_remap(blockIdx.x, ntiles * p.splits);
-    const int split = bid / ntiles, tile = bid % ntiles;
-    const int tp = tile / ntq, tq = tile % ntq;
-    const int p0 = tp * TP, q0 = tq * TQ;
-    const int nk_total = (p.M + BK - 1) / BK;
-    const int kt0 = split * p.kt_per_split;
-    int nk = nk_total - kt0;
-    if (nk > p.kt_per_split) nk = p.kt_per_split;
-    const int mbeg = kt0 * BK;
-
-    // Descriptors based at (first row of this split, first column of the tile).  Rows >= M are past the end
-    // of the range and read as zero, which is what the reduction needs for the M tail.
-    const bf16_t* Ab = p.A + (int64_t)mbeg * p.lda + p0;
-    const bf16_t* Bb = p.B + (int64_t)mbeg * p.ldb + q0;
-    int64_t a_bytes = ((int64_t)(p.M - mbeg) * p.lda - p0) * 2;
-    int64_t b_bytes = ((int64_t)(p.M - mbeg) * p.ldb - q0) * 2;
-    if (a_bytes < 0) a_bytes = 0;
-    if (b_bytes < 0) b_bytes = 0;
-    const auto rsA = make_rsrc(Ab, (uint32_t)(a_bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : a_bytes));
-    const auto rsB = make_rsrc(Bb, (uint32_t)(b_bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : b_bytes));
-
-    // DMA: one wave instruction = 2 tile rows (m) x 512 B.  Wave w fills rows w*8 .. w*8+7 of A and of B.
-    uint32_t voffA[4], voffB[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = (wave * 4 + i) * 2 + (lane >> 5);
-        const int c = (lane & 31) ^ tn_swz(m);
-        voffA[i] = (uint32_t)(m * p.lda * 2 + c * 16);
-        voffB[i] = (uint32_t)(m * p.ldb * 2 + c * 16);
-    }
-    const uint32_t kstepA = (uint32_t)(BK * p.lda * 2), kstepB = (uint32_t)(BK * p.ldb * 2);
-    auto stage_load = [&](int stage, int kt) {
-        char* sA = smem + stage * STAGE_BYTES + wave * 4096;
-        char* sB = sA + OP_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) lds_dma16(rsA, sA + i * 1024, voffA[i], (uint32_t)kt * kstepA);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) lds_dma16(rsB, sB + i * 1024, voffB[i], (uint32_t)kt * kstepB);
-    };
-
-    // Transposed fragment reads.  Lane l: g = l>>4 owns k-slots 8g..8g+7 (tile rows ks*32 + 8g + 0..7),
-    // within the group lane 4*qq+pp supplies row qq (first read) / 4+qq (second), columns 4pp..4pp+3 of the
-    // 16-column block; it receives column (l&15), rows 0..3 / 4..7.
-    const int g = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
-    uint32_t rdoff[2][2];   // [ks][half] byte offset of this lane's address for column block 0 of the tile
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int m = ks * 32 + 8 * g + 4 * h + qq;
-            rdoff[ks][h] = (uint32_t)(m * 512 + (((pp >> 1) ^ tn_swz(m)) << 4) + (pp & 1) * 8);
-        }
-    // Column block cb (16 columns = 2 chunks) adds (2*cb) to the logical chunk; since tn_swz only touches
-    // bits 1..3 and 2*cb has bit 0 clear, (c0 + 2cb) ^ s == (c0 ^ s) ^ (2cb)  ->  XOR the byte offset with cb<<5.
-    const uint32_t lds0 = lds_offset(smem);
-    auto frag = [&](uint32_t tile, int ks, int cb) -> bf16x8 {      // raw (asm) reads: see lds_read_tr16_pair_raw in common.h
-        return lds_read_tr16_pair_raw(tile + (rdoff[ks][0] ^ (uint32_t)(cb << 5)), tile + (rdoff[ks][1] ^ (uint32_t)(cb << 5)));
-    };
-
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // Column sums of A over the token dimension ride along: the A tile is in LDS anyway.  Thread t owns column
-    // (t & 255) and the rows of half (t >> 8) of every K-tile; only the workgroups of the first Q tile do it.
-    // Column sums of A ride along.  The ntq workgroups that share an A tile take turns (K-tile kt belongs to workgroup
-    // kt % ntq), and a thread sums 8 columns (one 16-B chunk) of 4 rows per K-tile with ds_read_b128 -- the first version
-    // (the tq == 0 workgroups alone, 32 two-byte reads per thread and K-tile) made those workgroups, and with them the
-    // whole launch, 15-25 % slower.
-    const bool do_colsum = p.colsum != nullptr;
-    const int cs_chunk = tid & 31, cs_rg = tid >> 5;
-    float cs_acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) cs_acc[e] = 0.f;
-    if (nk > 0) {
-        stage_load(0, 0);
-        __syncthreads();
-        int cur = 0;
-        for (int kt = 0; kt < nk; ++kt) {
-            if (kt + 1 < nk) stage_load(cur ^ 1, kt + 1);
-            const char* sA = smem + cur * STAGE_BYTES;
-            const char* sB = sA + OP_BYTES;
-            if (do_colsum && (kt % ntq) == tq) {
-#pragma unroll
-                for (int k4 = 0; k4 < 4; ++k4) {
-                    const int m = cs_rg + 16 * k4;
-                    const bf16x8 v = *(const bf16x8*)(sA + m * 512 + ((cs_chunk ^ tn_swz(m)) << 4));
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) cs_acc[e] += (float)v[e];
-                }
-            }
-            // Explicit fragment pipeline (same as the NT kernel): the B fragments of the whole K-tile first, the A
-            // fragments in a 3-deep register ring two MFMA groups ahead of their use.  The transposed reads go through
-            // inline asm (the builtin would make hipcc drain the LDS-DMA of the NEXT stage, issued just above, before
-            // touching this one), so the lgkmcnt waits are explicit: LDS results return in order, a fragment = 2 reads.
-            const uint32_t tA = lds0 + (uint32_t)(cur * STAGE_BYTES), tB = tA + OP_BYTES;
-            bf16x8 fq[2][4], fp[3];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) fq[ks][j] = frag(tB, ks, wq * 4 + j);
-            fp[0] = frag(tA, 0, wp * 8 + 0);
-            fp[1] = frag(tA, 0, wp * 8 + 1);
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const int ks = t >> 3, i = t & 7;
-                if (t + 2 < 16) fp[(t + 2) % 3] = frag(tA, (t + 2) >> 3, wp * 8 + ((t + 2) & 7));
-                // outstanding behind fragment t: the fragments of groups t+1 and t+2 (2 reads each)
-                if (t + 2 < 16) lds_raw_wait<4>(); else if (t + 1 < 16) lds_raw_wait<2>(); else lds_raw_wait<0>();
-                lds_raw_use(fp[t % 3]);
-                if (t == 0) {
-#pragma unroll
-                    for (int k2 = 0; k2 < 2; ++k2)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) lds_raw_use(fq[k2][j]);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fq[ks][j], fp[t % 3], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __syncthreads();
-            cur ^= 1;
-        }
-    }
-
-    if (do_colsum) {      // all LDS reads of the loop are behind its last barrier: reuse the front of the buffer
-        float* red = (float*)smem;                     // [16 row groups][256 columns]
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[cs_rg * 256 + cs_chunk * 8 + e] = cs_acc[e];
-        __syncthreads();
-        if (tid < 256) {
-            float sum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sum += red[r * 256 + tid];
-            p.colsum[((int64_t)split * ntq + tq) * (ntp * TP) + p0 + tid] = sum;
-        }
-    }
-    // lane holds C[p = p0 + wp*128 + i*16 + (lane&15)][q = q0 + wq*64 + j*16 + (lane>>4)*4 + 0..3]
-    const int frow = lane & 15;
-    if (p.direct) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int pr = p0 + wp * 128 + i * 16 + frow;
-            if (pr >= p.P) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int qc = q0 + wq * 64 + j * 16 + g * 4;
-                if (qc < p.Q) *(f32x4*)(p.out + (int64_t)pr * p.ldo + qc) = acc[i][j];
-            }
-        }
-    } else {
-        float* slab = p.out + ((int64_t)split * ntiles + tile) * (TP * TQ);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                *(f32x4*)(slab + (wp * 128 + i * 16 + frow) * TQ + wq * 64 + j * 16 + g * 4) = acc[i][j];
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// Ping-pong variant (same idea as gemm_nt_pp_kernel, see gemm_nt.hip): the two wave groups (wp = 0: output rows p0..p0+127,
-// wp = 1: p0+128..p0+255) run the same stream half a K-tile apart, so that one group's LDS-DMA issue burst overlaps the
+// The ping-pong stream (same idea as gemm_nt_pp_kernel, see gemm_nt.hip): the two wave groups (grp = 0: output rows p0..p0+127,
+// grp = 1: p0+128..p0+255) run the same stream half a K-tile apart, so that one group's LDS-DMA issue burst overlaps the
 // other group's MFMAs on every SIMD.  A columns are private to a group (two [64 m][128 p] stages of 16 KiB each, filled by the
 // group one K-tile ahead); B is read by both groups and lives in a ring of three [64 m][256 q] slots (group 0 fills tile rows
 // 0-31 of slot k+1, group 1 rows 32-63 of slot k+2, each at the start of ITS K-tile k).  Waits before the barrier that ends
@@ -216,33 +47,99 @@ constexpr int PP_B_BASE = 4 * PP_A_STAGE;                // [group][stage]
 constexpr int PP_B_SLOT = BK * TQ * 2;                   // 32 KiB
 constexpr int PP_LDS_BYTES = PP_B_BASE + 3 * PP_B_SLOT;  // 160 KiB
 
+// the output tile and the K-tiles of a workgroup: block -> (split, tile); K-tiles kt0 .. kt0 + nk - 1 of BKT tokens from row mbeg
+struct TnBlock { int ntp, ntq, ntiles, split, tile, tq, p0, q0, kt0, nk, mbeg; };
+template <int BKT>
+__device__ __forceinline__ TnBlock tn_decode(const TnProblem& p, int block) {
+    TnBlock b;
+    b.ntq = (p.Q + TQ - 1) / TQ;
+    b.ntp = (p.P + TP - 1) / TP;
+    b.ntiles = b.ntp * b.ntq;
+    const int bid = xcd_remap(block, b.ntiles * p.splits);
+    b.split = bid / b.ntiles;
+    b.tile = bid % b.ntiles;
+    b.tq = b.tile % b.ntq;
+    b.p0 = b.tile / b.ntq * TP;
+    b.q0 = b.tq * TQ;
+    b.kt0 = b.split * p.kt_per_split;
+    b.nk = (p.M + BKT - 1) / BKT - b.kt0;
+    if (b.nk > p.kt_per_split) b.nk = p.kt_per_split;
+    b.mbeg = b.kt0 * BKT;
+    return b;
+}
+
+// Descriptor based at (first row of the split, column `col`) of an [M, ld] operand, clipped to the end of the matrix (and to the 4 GiB
+// a descriptor can span): rows >= M are past the end of the range and read as zero, which is what the reduction needs for the M tail.
+template <typename T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tn_clipped_rsrc(const T* base, int64_t ld, int M, int mbeg, int col) {
+    int64_t bytes = ((int64_t)(M - mbeg) * ld - col) * (int64_t)sizeof(T);
+    if (bytes < 0) bytes = 0;
+    return make_rsrc(base + (int64_t)mbeg * ld + col, (uint32_t)(bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : bytes));
+}
+
+// The end of the column sums.  Every wave has issued its last (unused) fills; once they have landed, the group's own idle A stages serve
+// as the reduction buffer [ROWS row groups][128 columns] fp32: a thread leaves its N partials at (row, col ..), thread tl < 128 of the
+// group sums column tl.  Called by all threads, column sums or not: the barriers also realign the two groups.
+template <int ROWS, int N>
+__device__ __forceinline__ void tn_colsum_finish(const TnProblem& p, const TnBlock& b, char* smem, int grp, const float (&cs_acc)[N], int row,
+                                                 int col) {
+    // the (unused) fills issued by the last K-tiles must have landed in this group's A stages before they are reused
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    float* red = (float*)(smem + grp * (2 * PP_A_STAGE));
+    const bool do_colsum = p.colsum != nullptr;
+    if (do_colsum) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) red[row * 128 + col + e] = cs_acc[e];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (grp == 0) __builtin_amdgcn_s_barrier();          // pairs with group 1's last barrier
+    const int tl = threadIdx.x & 255;
+    if (do_colsum && tl < 128) {
+        float sum = 0.f;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) sum += red[r * 128 + tl];
+        p.colsum[((int64_t)b.split * b.ntq + b.tq) * (b.ntp * TP) + b.p0 + grp * 128 + tl] = sum;
+    }
+}
+
+// lane holds C[p = p0 + grp*128 + i*16 + (lane&15)][q = q0 + wl*64 + j*16 + (lane>>4)*4 + 0..3]: into C, clipped, or whole into the slab
+__device__ __forceinline__ void tn_store_tile(const TnProblem& p, const TnBlock& b, int grp, int wl, int lane, const f32x4 (&acc)[8][4]) {
+    const int frow = lane & 15, g = lane >> 4;
+    if (p.direct) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int pr = b.p0 + grp * 128 + i * 16 + frow;
+            if (pr >= p.P) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int qc = b.q0 + wl * 64 + j * 16 + g * 4;
+                if (qc < p.Q) *(f32x4*)(p.out + (int64_t)pr * p.ldo + qc) = acc[i][j];
+            }
+        }
+    } else {
+        float* slab = p.out + ((int64_t)b.split * b.ntiles + b.tile) * (TP * TQ);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                *(f32x4*)(slab + (grp * 128 + i * 16 + frow) * TQ + wl * 64 + j * 16 + g * 4) = acc[i][j];
+    }
+}
+
 __device__ __forceinline__ void tn_pp_body(const GemmTN& p, int block, char* smem) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wl = wave & 3;            // grp = wp, wl = wq
 
-    const int ntq = (p.Q + TQ - 1) / TQ, ntp = (p.P + TP - 1) / TP;
-    const int ntiles = ntp * ntq;
-    const int bid = xcd_remap(block, ntiles * p.splits);
-    const int split = bid / ntiles, tile = bid % ntiles;
-    const int tp = tile / ntq, tq = tile % ntq;
-    const int p0 = tp * TP, q0 = tq * TQ;
-    const int nk_total = (p.M + BK - 1) / BK;
-    const int kt0 = split * p.kt_per_split;
-    int nk = nk_total - kt0;
-    if (nk > p.kt_per_split) nk = p.kt_per_split;
-    const int mbeg = kt0 * BK;
+    const TnBlock blk = tn_decode<BK>(p, block);
+    const int ntq = blk.ntq, tq = blk.tq, nk = blk.nk;
 
-    // descriptors: A based at this group's first column, B at the tile's first column; rows >= M read as zero
-    const bf16_t* Ab = p.A + (int64_t)mbeg * p.lda + p0 + grp * 128;
-    const bf16_t* Bb = p.B + (int64_t)mbeg * p.ldb + q0;
-    int64_t a_bytes = ((int64_t)(p.M - mbeg) * p.lda - p0 - grp * 128) * 2;
-    int64_t b_bytes = ((int64_t)(p.M - mbeg) * p.ldb - q0) * 2;
-    if (a_bytes < 0) a_bytes = 0;
-    if (b_bytes < 0) b_bytes = 0;
-    const auto rsA = make_rsrc(Ab, (uint32_t)(a_bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : a_bytes));
-    const auto rsB = make_rsrc(Bb, (uint32_t)(b_bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : b_bytes));
+    // descriptors: A based at this group's first column, B at the tile's first column
+    const auto rsA = tn_clipped_rsrc(p.A, p.lda, p.M, blk.mbeg, blk.p0 + grp * 128);
+    const auto rsB = tn_clipped_rsrc(p.B, p.ldb, p.M, blk.mbeg, blk.q0);
 
     // DMA.  A: one instruction = 4 tile rows x 256 B; wave wl of a group fills rows wl*16 .. wl*16+15 of the group's stage.
     //       B: one instruction = 2 tile rows x 512 B; wave w fills rows w*8 .. w*8+7 of the slot (group 0: 0-31, group 1: 32-63).
@@ -266,7 +163,11 @@ __device__ __forceinline__ void tn_pp_body(const GemmTN& p, int block, char* sme
         for (int i = 0; i < 4; ++i) lds_dma16(rsB, ldsB + slot * PP_B_SLOT + i * 1024, voffB[i], (uint32_t)kt * kstepB);
     };
 
-    // transposed fragment reads (see gemm_tn_kernel): A rows are 256 B here, B rows 512 B
+    // Transposed fragment reads (A rows are 256 B here, B rows 512 B).  Lane l: g = l>>4 owns k-slots 8g..8g+7 (tile rows
+    // ks*32 + 8g + 0..7), within the group lane 4*qq+pp supplies row qq (first read) / 4+qq (second), columns 4pp..4pp+3 of the
+    // 16-column block; it receives column (l&15), rows 0..3 / 4..7.  rd?[ks][half]: byte offset of this lane's address for column
+    // block 0.  Column block cb (16 columns = 2 chunks) adds 2*cb to the logical chunk; since tn_swz only touches bits 1..3 and 2*cb
+    // has bit 0 clear, (c0 + 2cb) ^ s == (c0 ^ s) ^ (2cb)  ->  XOR the byte offset with cb<<5.
     const int g = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
     uint32_t rdA[2][2], rdB[2][2];
 #pragma unroll
@@ -287,7 +188,9 @@ __device__ __forceinline__ void tn_pp_body(const GemmTN& p, int block, char* sme
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // column sums of A (bias gradient): each group sums its own 128 columns; the ntq workgroups sharing an A tile take turns
+    // column sums of A (bias gradient) ride along, the A tile is in LDS anyway: each group sums its own 128 columns, a thread 8 columns
+    // (one 16-B chunk) of 4 rows per K-tile.  The ntq workgroups sharing an A tile take turns (K-tile kt belongs to workgroup kt % ntq):
+    // left to the tq == 0 workgroups alone it made those, and with them the whole launch, 15-25 % slower
     const bool do_colsum = p.colsum != nullptr;
     const int tl = tid & 255;
     const int cs_chunk = tl & 15, cs_rg = tl >> 4;
@@ -361,45 +264,8 @@ __device__ __forceinline__ void tn_pp_body(const GemmTN& p, int block, char* sme
         __builtin_amdgcn_s_barrier();
         slot = slot1;
     }
-    // the (unused) fills issued by the last K-tiles must have landed in this group's A stages before they are reused
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    // column-sum partials: the group's own (now idle) A stages serve as the reduction buffer
-    float* red = (float*)(smem + grp * (2 * PP_A_STAGE));        // [16 row groups][128 columns] fp32 = 8 KiB
-    if (do_colsum) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[cs_rg * 128 + cs_chunk * 8 + e] = cs_acc[e];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (grp == 0) __builtin_amdgcn_s_barrier();          // pairs with group 1's last barrier
-    if (do_colsum && tl < 128) {
-        float sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum += red[r * 128 + tl];
-        p.colsum[((int64_t)split * ntq + tq) * (ntp * TP) + p0 + grp * 128 + tl] = sum;
-    }
-    // lane holds C[p = p0 + grp*128 + i*16 + (lane&15)][q = q0 + wl*64 + j*16 + (lane>>4)*4 + 0..3]
-    const int frow = lane & 15;
-    if (p.direct) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int pr = p0 + grp * 128 + i * 16 + frow;
-            if (pr >= p.P) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int qc = q0 + wl * 64 + j * 16 + g * 4;
-                if (qc < p.Q) *(f32x4*)(p.out + (int64_t)pr * p.ldo + qc) = acc[i][j];
-            }
-        }
-    } else {
-        float* slab = p.out + ((int64_t)split * ntiles + tile) * (TP * TQ);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                *(f32x4*)(slab + (grp * 128 + i * 16 + frow) * TQ + wl * 64 + j * 16 + g * 4) = acc[i][j];
-    }
+    tn_colsum_finish<16>(p, blk, smem, grp, cs_acc, cs_rg, cs_chunk * 8);          // [16 row groups][128 columns] fp32 = 8 KiB
+    tn_store_tile(p, blk, grp, wl, lane, acc);
 }
 
 __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(GemmTN p) {
@@ -438,16 +304,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_pair_kernel(GemmTNPair pr) 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 template <int V> struct Int { static constexpr int value = V; };
 
-struct GemmTN8 {
-    const uint8_t* A; const uint8_t* B; const uint8_t* sa; const uint8_t* sb; float* out;
-    int64_t lda, ldb, ldo;       // lda / ldb: bytes per token row (= columns of the quantised matrices: their scale layouts' row length)
-    int M, P, Q;
-    int splits, kt_per_split;    // in K-tiles of 128 tokens
-    int direct;
-    float* colsum;               // optional [splits * ntq][ntp * 256]: partial column sums of dequant(A) (the bias gradient of the same Linear)
-};
+struct GemmTN8 : TnProblem { const uint8_t* A; const uint8_t* B; const uint8_t* sa; const uint8_t* sb; };
 
-constexpr int BK8 = 128;
 
 // the four transposed reads of one fragment: one address register, the other three rows 8 / 64 / 72 tile rows further as instruction
 // offsets (STEP = 8 rows in bytes: 1024 on the 128-byte rows of A, 2048 on the 256-byte rows of B)
@@ -472,26 +330,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_pp_kernel(GemmTN8 p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wl = wave & 3;
 
-    const int ntq = (p.Q + TQ - 1) / TQ, ntp = (p.P + TP - 1) / TP;
-    const int ntiles = ntp * ntq;
-    const int bid = xcd_remap((int)blockIdx.x, ntiles * p.splits);
-    const int split = bid / ntiles, tile = bid % ntiles;
-    const int tp = tile / ntq, tq = tile % ntq;
-    const int p0 = tp * TP, q0 = tq * TQ;
-    const int nk_total = (p.M + BK8 - 1) / BK8;
-    const int kt0 = split * p.kt_per_split;
-    int nk = nk_total - kt0;
-    if (nk > p.kt_per_split) nk = p.kt_per_split;
-    const int mbeg = kt0 * BK8;
+    const TnBlock blk = tn_decode<BK8>(p, (int)blockIdx.x);
+    const int ntq = blk.ntq, tq = blk.tq, p0 = blk.p0, q0 = blk.q0, kt0 = blk.kt0, nk = blk.nk;
 
-    const uint8_t* Ab = p.A + (int64_t)mbeg * p.lda + p0 + grp * 128;
-    const uint8_t* Bb = p.B + (int64_t)mbeg * p.ldb + q0;
-    int64_t a_bytes = (int64_t)(p.M - mbeg) * p.lda - p0 - grp * 128;
-    int64_t b_bytes = (int64_t)(p.M - mbeg) * p.ldb - q0;
-    if (a_bytes < 0) a_bytes = 0;
-    if (b_bytes < 0) b_bytes = 0;
-    const auto rsA = make_rsrc(Ab, (uint32_t)(a_bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : a_bytes));
-    const auto rsB = make_rsrc(Bb, (uint32_t)(b_bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : b_bytes));
+    const auto rsA = tn_clipped_rsrc(p.A, p.lda, p.M, blk.mbeg, p0 + grp * 128);
+    const auto rsB = tn_clipped_rsrc(p.B, p.ldb, p.M, blk.mbeg, q0);
 
     // DMA.  A: one instruction = 8 tile rows x 128 B; wave wl of a group fills rows wl*32 .. wl*32+31 of the group's stage.
     //       B: one instruction = 4 tile rows x 256 B; wave w fills rows w*16 .. w*16+15 of the slot (group 0: 0-63, group 1: 64-127).
@@ -674,43 +517,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_pp_kernel(GemmTN8 p) {
         cs_turn = cs_turn == 0 ? ntq - 1 : cs_turn - 1;
     }
 #undef VIPANT_TN8_MX
-    // the (unused) fills issued by the last K-tiles must have landed in this group's A stages before they are reused
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    // column-sum partials: the group's own (now idle) A stages serve as the reduction buffer, [8 row groups][128 columns] fp32 = 4 KiB
-    float* red = (float*)(smem + grp * (2 * PP_A_STAGE));
-    const int tl = tid & 255;
-    if (do_colsum) *(f32x4*)(red + (wl * 2 + (lane >> 5)) * 128 + cs_c * 4) = f32x4{cs_acc[0], cs_acc[1], cs_acc[2], cs_acc[3]};
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (grp == 0) __builtin_amdgcn_s_barrier();          // pairs with group 1's last barrier
-    if (do_colsum && tl < 128) {
-        float sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) sum += red[r * 128 + tl];
-        p.colsum[((int64_t)split * ntq + tq) * (ntp * TP) + p0 + grp * 128 + tl] = sum;
-    }
-    // lane holds C[p = p0 + grp*128 + i*16 + (lane&15)][q = q0 + wl*64 + j*16 + (lane>>4)*4 + 0..3]
-    const int frow = lane & 15, g = lane >> 4;
-    if (p.direct) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int pr = p0 + grp * 128 + i * 16 + frow;
-            if (pr >= p.P) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int qc = q0 + wl * 64 + j * 16 + g * 4;
-                if (qc < p.Q) *(f32x4*)(p.out + (int64_t)pr * p.ldo + qc) = acc[i][j];
-            }
-        }
-    } else {
-        float* slab = p.out + ((int64_t)split * ntiles + tile) * (TP * TQ);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                *(f32x4*)(slab + (grp * 128 + i * 16 + frow) * TQ + wl * 64 + j * 16 + g * 4) = acc[i][j];
-    }
+    tn_colsum_finish<8>(p, blk, smem, grp, cs_acc, wl * 2 + (lane >> 5), cs_c * 4);          // [8 row groups][128 columns] fp32 = 4 KiB
+    tn_store_tile(p, blk, grp, wl, lane, acc);
 }
 
 __device__ __forceinline__ void tn_reduce_blocks(const float* slab, float* C, int64_t ldc, int P, int Q, int splits, int accumulate,
@@ -775,230 +583,132 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_both_kernel(const float* s
     else colsum_reduce_block(cs_part, cs_out, P, cs_stride, cs_parts, accumulate, (int)blockIdx.x - nred);
 }
 
-void plan_tiles(int64_t M, int64_t tiles, int* splits, int* kt_per_split) {
-    const int64_t nk = ceil_div(M, BK);
-    int64_t s = 256 / tiles;
-    if (s < 1) s = 1;
-    if (s > nk) s = nk;
-    const int64_t per = ceil_div(nk, s);
-    *splits = (int)ceil_div(nk, per);
-    *kt_per_split = (int)per;
+// ---------------------------------------------------------------------------------------------------------
+// host side: what the three entry points differ in, and what they share
+struct TnFormat {
+    const char* op;
+    int bk, es;                // tokens per K-tile, bytes per operand element
+    int p_unit, q_unit;        // P and Q are multiples of these
+    int ld_unit;               // lda and ldb are multiples of this (in elements): 16 bytes of bf16 | a column group of the e4m3 scale layout
+    int problems;
+};
+constexpr TnFormat TN_BF16{"gemm_tn", BK, 2, 1, 4, 8, 1}, TN_E4M3{"gemm_tn_e4m3", BK8, 1, 128, 128, 128, 1}, TN_PAIR{"gemm_tn_pair", BK, 2, 1, 4, 8, 2};
+
+// VIPANT_TN_SPLIT is read per call: tests and A/B scripts switch it inside one process
+TnPlan tn_plan_of(const TnFormat& f, int64_t M, int64_t P, int64_t Q, bool accumulate) {
+    return tn_plan(M, P, Q, f.bk, f.problems, tn_split_factor(getenv("VIPANT_TN_SPLIT")), accumulate);
 }
 
-// VIPANT_TN_SPLIT=k (experiment, default 1): k times as many, k times shorter workgroups per weight-gradient launch -- several per CU
-// instead of one long one, so that CUs another stream's kernel holds (the replica group's all-reduce) cost a launch 1/k of a workgroup's
-// time at its tail instead of a whole one; the price is k times the partial tiles to write and reduce (profiles/r6_comm_shadow_cfg5.md)
-int64_t split_factor() {
-    const char* e = getenv("VIPANT_TN_SPLIT");
-    const int k = e ? atoi(e) : 1;
-    return k < 1 ? 1 : (k > 8 ? 8 : k);
+// the argument checks, in the order shape, leading dimensions, alignment, descriptor range, workspace; leaves the plan in *pl
+int32_t tn_check(const TnFormat& f, int64_t M, int64_t P, int64_t Q, int64_t lda, int64_t ldb, int64_t ldc, std::initializer_list<const void*> operands,
+                 bool accumulate, bool needs_workspace, const void* workspace, size_t workspace_bytes, TnPlan* pl) {
+    VIPANT_REQUIRE(M > 0 && P > 0 && Q > 0, VIPANT_EBADSHAPE, "%s: empty problem", f.op);
+    VIPANT_REQUIRE(P % f.p_unit == 0 && Q % f.q_unit == 0, VIPANT_EBADSHAPE, "%s: need P %% %d == 0 and Q %% %d == 0 (P=%ld Q=%ld)", f.op, f.p_unit,
+                   f.q_unit, (long)P, (long)Q);
+    VIPANT_REQUIRE(lda >= P && ldb >= Q && ldc >= Q && lda % f.ld_unit == 0 && ldb % f.ld_unit == 0 && ldc % 4 == 0, VIPANT_EALIGN,
+                   "%s: bad leading dims (lda, ldb: multiples of %d elements; ldc: of 4)", f.op, f.ld_unit);
+    for (const void* ptr : operands)
+        VIPANT_REQUIRE(ptr != nullptr && (uintptr_t)ptr % 16 == 0, VIPANT_EALIGN, "%s: operands (and block scales) must be 16-byte aligned", f.op);
+    *pl = tn_plan_of(f, M, P, Q, accumulate);
+    // a split's descriptors span its K-tiles and what the fills read ahead of them: 32-bit offsets
+    VIPANT_REQUIRE((int64_t)(pl->per + 3) * f.bk * (lda > ldb ? lda : ldb) * f.es < (1ll << 32), VIPANT_EBADSHAPE,
+                   "%s: per-split byte range exceeds 4 GiB", f.op);
+    if (needs_workspace || !pl->direct)
+        VIPANT_REQUIRE(workspace != nullptr && workspace_bytes >= pl->workspace_bytes, VIPANT_ENOWORKSPACE, "%s: workspace too small (%zu < %zu)",
+                       f.op, workspace_bytes, pl->workspace_bytes);
+    return VIPANT_OK;
 }
 
-void plan(int64_t M, int64_t P, int64_t Q, int* splits, int* kt_per_split) {
-    const int64_t tiles = ceil_div(P, TP) * ceil_div(Q, TQ);
-    const int64_t nk = ceil_div(M, BK);
-    int64_t s = 256 / tiles * (tiles <= 256 ? split_factor() : 1);
-    if (s < 1) s = 1;
-    if (s > nk) s = nk;
-    const int64_t per = ceil_div(nk, s);
-    *splits = (int)ceil_div(nk, per);
-    *kt_per_split = (int)per;
+// the dynamic-LDS opt-in of a ping-pong kernel, once per device
+int32_t tn_lds_opt_in(DeviceOnce& once, const void* kernel) {
+    if (first_on_device(once)) {
+        VIPANT_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES));
+        done_on_device(once);
+    }
+    return VIPANT_OK;
 }
 
-// the e4m3 kernel: K-tiles of 128 tokens
-void plan8(int64_t M, int64_t P, int64_t Q, int* splits, int* kt_per_split) {
-    const int64_t tiles = ceil_div(P, TP) * ceil_div(Q, TQ);
-    const int64_t nk = ceil_div(M, BK8);
-    int64_t s = 256 / tiles * (tiles <= 256 ? split_factor() : 1);
-    if (s < 1) s = 1;
-    if (s > nk) s = nk;
-    const int64_t per = ceil_div(nk, s);
-    *splits = (int)ceil_div(nk, per);
-    *kt_per_split = (int)per;
+TnProblem tn_problem(const TnPlan& pl, float* C, int64_t ldc, float* slab, int64_t lda, int64_t ldb, int64_t M, int64_t P, int64_t Q, float* cs_part) {
+    return TnProblem{pl.direct ? C : slab, lda, ldb, pl.direct ? ldc : TQ, (int)M, (int)P, (int)Q, pl.splits, pl.per, pl.direct ? 1 : 0, cs_part};
+}
+
+// the reductions behind the contraction kernel: the splits' slabs into C (nothing for a direct plan) and the column-sum partials into
+// a_colsum, as ONE launch where both are due; slab1 / C1: the second problem of a pair (grid.y = 2)
+int32_t tn_reduce(const TnPlan& pl, const float* slab, float* C, int64_t ldc, int64_t P, int64_t Q, int accumulate, const float* cs_part, float* a_colsum,
+                  hipStream_t s, const float* slab1 = nullptr, float* C1 = nullptr) {
+    const unsigned cs_blocks = (unsigned)ceil_div(P, 64);
+    if (!pl.direct && a_colsum != nullptr) {
+        hipLaunchKernelGGL(gemm_tn_reduce_both_kernel, dim3((unsigned)pl.reduce_blocks + cs_blocks), dim3(256), 0, s, slab, C, ldc, (int)P, (int)Q,
+                           pl.splits, accumulate, pl.reduce_blocks, cs_part, a_colsum, pl.cs_stride, pl.cs_parts);
+        VIPANT_LAUNCH_CHECK();
+        return VIPANT_OK;
+    }
+    if (!pl.direct) {
+        hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3(pl.reduce_blocks, slab1 != nullptr ? 2 : 1), dim3(256), 0, s, slab, C, ldc, (int)P, (int)Q, pl.splits,
+                           accumulate, slab1, C1);
+        VIPANT_LAUNCH_CHECK();
+    }
+    if (a_colsum != nullptr) {
+        hipLaunchKernelGGL(gemm_tn_colsum_reduce_kernel, dim3(cs_blocks), dim3(256), 0, s, cs_part, a_colsum, (int)P, pl.cs_stride, pl.cs_parts, accumulate);
+        VIPANT_LAUNCH_CHECK();
+    }
+    return VIPANT_OK;
 }
 
 }  // namespace
 
-extern "C" size_t vipant_gemm_tn_workspace_bytes(int64_t M, int64_t P, int64_t Q) {
-    int splits, per;
-    plan(M, P, Q, &splits, &per);
-    return (size_t)splits * (size_t)(ceil_div(P, TP) * ceil_div(Q, TQ)) * TP * TQ * sizeof(float) +
-           (size_t)splits * (size_t)ceil_div(Q, TQ) * (size_t)ceil_div(P, TP) * TP * sizeof(float);
-}
+extern "C" size_t vipant_gemm_tn_workspace_bytes(int64_t M, int64_t P, int64_t Q) { return tn_plan_of(TN_BF16, M, P, Q, false).workspace_bytes; }
+extern "C" size_t vipant_gemm_tn_e4m3_workspace_bytes(int64_t M, int64_t P, int64_t Q) { return tn_plan_of(TN_E4M3, M, P, Q, false).workspace_bytes; }
+extern "C" size_t vipant_gemm_tn_pair_workspace_bytes(int64_t M, int64_t P, int64_t Q) { return tn_plan_of(TN_PAIR, M, P, Q, false).workspace_bytes; }
 
 extern "C" int32_t vipant_gemm_tn(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C,
                                   int64_t ldc, int64_t M, int64_t P, int64_t Q, int32_t accumulate, float* a_colsum,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-    VIPANT_REQUIRE(M > 0 && P > 0 && Q > 0, VIPANT_EBADSHAPE, "gemm_tn: empty problem");
-    VIPANT_REQUIRE(Q % 4 == 0, VIPANT_EBADSHAPE, "gemm_tn: need Q%%4==0 (P=%ld Q=%ld)",
-                   (long)P, (long)Q);
-    VIPANT_REQUIRE(lda >= P && ldb >= Q && ldc >= Q && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, VIPANT_EALIGN,
-                   "gemm_tn: bad leading dims");
-    VIPANT_REQUIRE(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0), VIPANT_EALIGN,
-                   "gemm_tn: operands must be 16-byte aligned");
-    int splits, per;
-    plan(M, P, Q, &splits, &per);
-    VIPANT_REQUIRE((int64_t)(per + 3) * BK * (lda > ldb ? lda : ldb) * 2 < (1ll << 32), VIPANT_EBADSHAPE,
-                   "gemm_tn: per-split byte range exceeds 4 GiB");
-    const size_t need = vipant_gemm_tn_workspace_bytes(M, P, Q);
-    const int direct = (splits == 1 && !accumulate) ? 1 : 0;
-    if (!direct || a_colsum != nullptr)
-        VIPANT_REQUIRE(workspace != nullptr && workspace_bytes >= need, VIPANT_ENOWORKSPACE,
-                       "gemm_tn: workspace too small (%zu < %zu)", workspace_bytes, need);
+    TnPlan pl;
+    if (const int32_t rc = tn_check(TN_BF16, M, P, Q, lda, ldb, ldc, {A, B, C}, accumulate != 0, a_colsum != nullptr, workspace, workspace_bytes, &pl)) return rc;
     static DeviceOnce once;
-    static int variant = 0;
-    if (first_on_device(once)) {
-        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           2 * STAGE_BYTES));
-        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           PP_LDS_BYTES));
-        variant = vipant_switches();       // (read once per device here) VIPANT_SW_TWO_STAGE: the two-stage kernel
-        done_on_device(once);
-    }
+    if (const int32_t rc = tn_lds_opt_in(once, (const void*)gemm_tn_pp_kernel)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t tiles = ceil_div(P, TP) * ceil_div(Q, TQ);
-    const size_t slab_bytes = (size_t)splits * (size_t)tiles * TP * TQ * sizeof(float);
-    float* cs_part = a_colsum != nullptr ? (float*)((char*)workspace + slab_bytes) : nullptr;
-    GemmTN p{(const bf16_t*)A, (const bf16_t*)B, direct ? C : (float*)workspace, lda, ldb, direct ? ldc : TQ,
-             (int)M, (int)P, (int)Q, splits, per, direct, cs_part};
-    if (variant & VIPANT_SW_TWO_STAGE) hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)(tiles * splits)), dim3(512), 2 * STAGE_BYTES, s, p);
-    else hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3((unsigned)(tiles * splits)), dim3(512), PP_LDS_BYTES, s, p);
+    float* cs_part = a_colsum != nullptr ? (float*)((char*)workspace + pl.slab_bytes) : nullptr;
+    const GemmTN p{tn_problem(pl, C, ldc, (float*)workspace, lda, ldb, M, P, Q, cs_part), (const bf16_t*)A, (const bf16_t*)B};
+    hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3((unsigned)(pl.tiles * pl.splits)), dim3(512), PP_LDS_BYTES, s, p);
     VIPANT_LAUNCH_CHECK();
-    const int cs_parts = (int)(splits * ceil_div(Q, TQ)), cs_stride = (int)(ceil_div(P, TP) * TP);
-    if (!direct) {
-        const int64_t total4 = tiles * TP * TQ / 4;
-        int blocks = (int)ceil_div(total4, 256);
-        if (blocks > 2048) blocks = 2048;
-        if (a_colsum != nullptr) {       // one launch for both reductions
-            hipLaunchKernelGGL(gemm_tn_reduce_both_kernel, dim3((unsigned)(blocks + ceil_div(P, 64))), dim3(256), 0, s,
-                               (const float*)workspace, C, ldc, (int)P, (int)Q, splits, accumulate, blocks, (const float*)cs_part, a_colsum,
-                               cs_stride, cs_parts);
-            VIPANT_LAUNCH_CHECK();
-            return VIPANT_OK;
-        }
-        hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)workspace, C, ldc,
-                           (int)P, (int)Q, splits, accumulate);
-        VIPANT_LAUNCH_CHECK();
-    }
-    if (a_colsum != nullptr) {
-        hipLaunchKernelGGL(gemm_tn_colsum_reduce_kernel, dim3((unsigned)ceil_div(P, 64)), dim3(256), 0, s,
-                           (const float*)cs_part, a_colsum, (int)P, cs_stride, cs_parts, accumulate);
-        VIPANT_LAUNCH_CHECK();
-    }
-    return VIPANT_OK;
+    return tn_reduce(pl, (const float*)workspace, C, ldc, P, Q, accumulate, cs_part, a_colsum, s);
 }
 
 // C[P, Q] (+)= dequant(A, sa)^T dequant(B, sb) on e4m3 operands whose MX scales are uniform over 32-token x 32-column blocks.
-extern "C" size_t vipant_gemm_tn_e4m3_workspace_bytes(int64_t M, int64_t P, int64_t Q) {
-    int splits, per;
-    plan8(M, P, Q, &splits, &per);
-    return (size_t)splits * (size_t)(ceil_div(P, TP) * ceil_div(Q, TQ)) * TP * TQ * sizeof(float) +
-           (size_t)splits * (size_t)ceil_div(Q, TQ) * (size_t)ceil_div(P, TP) * TP * sizeof(float);
-}
-
 extern "C" int32_t vipant_gemm_tn_e4m3(const uint8_t* A, int64_t lda, const uint8_t* sa, const uint8_t* B, int64_t ldb, const uint8_t* sb,
                                        float* C, int64_t ldc, int64_t M, int64_t P, int64_t Q, int32_t accumulate, float* a_colsum,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-    VIPANT_REQUIRE(M > 0 && P > 0 && Q > 0, VIPANT_EBADSHAPE, "gemm_tn_e4m3: empty problem");
-    VIPANT_REQUIRE(P % 128 == 0 && Q % 128 == 0, VIPANT_EBADSHAPE, "gemm_tn_e4m3: need P %% 128 == 0 and Q %% 128 == 0 (P=%ld Q=%ld)",
-                   (long)P, (long)Q);
-    VIPANT_REQUIRE(lda >= P && ldb >= Q && ldc >= Q && lda % 128 == 0 && ldb % 128 == 0 && ldc % 4 == 0, VIPANT_EALIGN,
-                   "gemm_tn_e4m3: bad leading dims (lda, ldb: the full row length of the quantised matrices, a multiple of 128)");
-    VIPANT_REQUIRE(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0) && ((uintptr_t)sa % 16 == 0) &&
-                       ((uintptr_t)sb % 16 == 0) && sa != nullptr && sb != nullptr,
-                   VIPANT_EALIGN, "gemm_tn_e4m3: operands and their block scales must be 16-byte aligned");
-    int splits, per;
-    plan8(M, P, Q, &splits, &per);
-    VIPANT_REQUIRE((int64_t)(per + 3) * BK8 * (lda > ldb ? lda : ldb) < (1ll << 32), VIPANT_EBADSHAPE,
-                   "gemm_tn_e4m3: per-split byte range exceeds 4 GiB");
-    const size_t need = vipant_gemm_tn_e4m3_workspace_bytes(M, P, Q);
-    const int direct = (splits == 1 && !accumulate) ? 1 : 0;
-    if (!direct || a_colsum != nullptr)
-        VIPANT_REQUIRE(workspace != nullptr && workspace_bytes >= need, VIPANT_ENOWORKSPACE,
-                       "gemm_tn_e4m3: workspace too small (%zu < %zu)", workspace_bytes, need);
+    TnPlan pl;
+    if (const int32_t rc = tn_check(TN_E4M3, M, P, Q, lda, ldb, ldc, {A, B, C, sa, sb}, accumulate != 0, a_colsum != nullptr, workspace, workspace_bytes, &pl))
+        return rc;
     static DeviceOnce once;
-    if (first_on_device(once)) {
-        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn8_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES));
-        done_on_device(once);
-    }
+    if (const int32_t rc = tn_lds_opt_in(once, (const void*)gemm_tn8_pp_kernel)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t tiles = ceil_div(P, TP) * ceil_div(Q, TQ);
-    const size_t slab_bytes = (size_t)splits * (size_t)tiles * TP * TQ * sizeof(float);
-    float* cs_part = a_colsum != nullptr ? (float*)((char*)workspace + slab_bytes) : nullptr;
-    GemmTN8 p{A, B, sa, sb, direct ? C : (float*)workspace, lda, ldb, direct ? ldc : TQ, (int)M, (int)P, (int)Q, splits, per, direct, cs_part};
-    hipLaunchKernelGGL(gemm_tn8_pp_kernel, dim3((unsigned)(tiles * splits)), dim3(512), PP_LDS_BYTES, s, p);
+    float* cs_part = a_colsum != nullptr ? (float*)((char*)workspace + pl.slab_bytes) : nullptr;
+    const GemmTN8 p{tn_problem(pl, C, ldc, (float*)workspace, lda, ldb, M, P, Q, cs_part), A, B, sa, sb};
+    hipLaunchKernelGGL(gemm_tn8_pp_kernel, dim3((unsigned)(pl.tiles * pl.splits)), dim3(512), PP_LDS_BYTES, s, p);
     VIPANT_LAUNCH_CHECK();
-    const int cs_parts = (int)(splits * ceil_div(Q, TQ)), cs_stride = (int)(ceil_div(P, TP) * TP);
-    if (!direct) {
-        const int64_t total4 = tiles * TP * TQ / 4;
-        int blocks = (int)ceil_div(total4, 256);
-        if (blocks > 2048) blocks = 2048;
-        if (a_colsum != nullptr) {       // one launch for both reductions
-            hipLaunchKernelGGL(gemm_tn_reduce_both_kernel, dim3((unsigned)(blocks + ceil_div(P, 64))), dim3(256), 0, s,
-                               (const float*)workspace, C, ldc, (int)P, (int)Q, splits, accumulate, blocks, (const float*)cs_part, a_colsum,
-                               cs_stride, cs_parts);
-            VIPANT_LAUNCH_CHECK();
-            return VIPANT_OK;
-        }
-        hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)workspace, C, ldc, (int)P, (int)Q, splits,
-                           accumulate);
-        VIPANT_LAUNCH_CHECK();
-    }
-    if (a_colsum != nullptr) {
-        hipLaunchKernelGGL(gemm_tn_colsum_reduce_kernel, dim3((unsigned)ceil_div(P, 64)), dim3(256), 0, s, (const float*)cs_part, a_colsum,
-                           (int)P, cs_stride, cs_parts, accumulate);
-        VIPANT_LAUNCH_CHECK();
-    }
-    return VIPANT_OK;
+    return tn_reduce(pl, (const float*)workspace, C, ldc, P, Q, accumulate, cs_part, a_colsum, s);
 }
 
 // Two contractions of the same shape in one launch: C0 = A0^T . B0, C1 = A1^T . B1 (no accumulate, no column sums).
-extern "C" size_t vipant_gemm_tn_pair_workspace_bytes(int64_t M, int64_t P, int64_t Q) {
-    const int64_t tiles = ceil_div(P, TP) * ceil_div(Q, TQ);
-    int splits, per;
-    plan_tiles(M, 2 * tiles, &splits, &per);
-    return 2 * (size_t)splits * (size_t)tiles * TP * TQ * sizeof(float);
-}
-
 extern "C" int32_t vipant_gemm_tn_pair(const uint16_t* A0, const uint16_t* B0, float* C0, const uint16_t* A1, const uint16_t* B1,
                                        float* C1, int64_t lda, int64_t ldb, int64_t ldc, int64_t M, int64_t P, int64_t Q,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-    VIPANT_REQUIRE(M > 0 && P > 0 && Q > 0 && Q % 4 == 0, VIPANT_EBADSHAPE, "gemm_tn_pair: bad shape");
-    VIPANT_REQUIRE(lda >= P && ldb >= Q && ldc >= Q && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, VIPANT_EALIGN,
-                   "gemm_tn_pair: bad leading dims");
-    VIPANT_REQUIRE(((uintptr_t)A0 % 16 == 0) && ((uintptr_t)B0 % 16 == 0) && ((uintptr_t)C0 % 16 == 0) && ((uintptr_t)A1 % 16 == 0) &&
-                       ((uintptr_t)B1 % 16 == 0) && ((uintptr_t)C1 % 16 == 0), VIPANT_EALIGN, "gemm_tn_pair: operands must be 16-byte aligned");
-    const int64_t tiles = ceil_div(P, TP) * ceil_div(Q, TQ);
-    int splits, per;
-    plan_tiles(M, 2 * tiles, &splits, &per);
-    VIPANT_REQUIRE((int64_t)(per + 3) * BK * (lda > ldb ? lda : ldb) * 2 < (1ll << 32), VIPANT_EBADSHAPE,
-                   "gemm_tn_pair: per-split byte range exceeds 4 GiB");
-    VIPANT_REQUIRE(workspace != nullptr && workspace_bytes >= vipant_gemm_tn_pair_workspace_bytes(M, P, Q), VIPANT_ENOWORKSPACE,
-                   "gemm_tn_pair: workspace too small");
+    TnPlan pl;
+    if (const int32_t rc = tn_check(TN_PAIR, M, P, Q, lda, ldb, ldc, {A0, B0, C0, A1, B1, C1}, false, true, workspace, workspace_bytes, &pl)) return rc;
     static DeviceOnce once;
-    if (first_on_device(once)) {
-        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_pp_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES));
-        done_on_device(once);
-    }
+    if (const int32_t rc = tn_lds_opt_in(once, (const void*)gemm_tn_pp_pair_kernel)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int direct = splits == 1 ? 1 : 0;
     float* slab0 = (float*)workspace;
-    float* slab1 = slab0 + (size_t)splits * (size_t)tiles * TP * TQ;
+    float* slab1 = (float*)((char*)workspace + pl.slab_bytes);
     GemmTNPair pr;
-    pr.a = GemmTN{(const bf16_t*)A0, (const bf16_t*)B0, direct ? C0 : slab0, lda, ldb, direct ? ldc : TQ, (int)M, (int)P, (int)Q, splits, per,
-                  direct, nullptr};
-    pr.b = GemmTN{(const bf16_t*)A1, (const bf16_t*)B1, direct ? C1 : slab1, lda, ldb, direct ? ldc : TQ, (int)M, (int)P, (int)Q, splits, per,
-                  direct, nullptr};
-    pr.blocks_a = (int)(tiles * splits);
-    hipLaunchKernelGGL(gemm_tn_pp_pair_kernel, dim3((unsigned)(2 * tiles * splits)), dim3(512), PP_LDS_BYTES, s, pr);
+    pr.a = GemmTN{tn_problem(pl, C0, ldc, slab0, lda, ldb, M, P, Q, nullptr), (const bf16_t*)A0, (const bf16_t*)B0};
+    pr.b = GemmTN{tn_problem(pl, C1, ldc, slab1, lda, ldb, M, P, Q, nullptr), (const bf16_t*)A1, (const bf16_t*)B1};
+    pr.blocks_a = (int)(pl.tiles * pl.splits);
+    hipLaunchKernelGGL(gemm_tn_pp_pair_kernel, dim3((unsigned)(2 * pl.tiles * pl.splits)), dim3(512), PP_LDS_BYTES, s, pr);
     VIPANT_LAUNCH_CHECK();
-    if (!direct) {
-        const int64_t total4 = tiles * TP * TQ / 4;
-        int blocks = (int)ceil_div(total4, 256);
-        if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3(blocks, 2), dim3(256), 0, s, (const float*)slab0, C0, ldc, (int)P, (int)Q, splits, 0,
-                           (const float*)slab1, C1);
-        VIPANT_LAUNCH_CHECK();
-    }
-    return VIPANT_OK;
+    return tn_reduce(pl, slab0, C0, ldc, P, Q, 0, nullptr, nullptr, s, slab1, C1);
 }

@@ -7,7 +7,7 @@
 enum : int {
     VIPANT_SW_SKIP_STORES = 1 << 0,            // device, NT kernels: the tile epilogues store nothing (main-loop timing; results are garbage)
     // (bits 1-3 went with the round-2 persistent NT kernel)
-    VIPANT_SW_TWO_STAGE = 1 << 4,              // the round-1 two-stage kernels: NT staged bf16-family launches on the plain kernel, TN on gemm_tn_kernel
+    VIPANT_SW_TWO_STAGE = 1 << 4,              // NT: staged bf16-family launches on the round-1 two-stage (plain) kernel; the two-stage TN kernel it also selected is gone
     VIPANT_SW_GROUPED_ALWAYS = 1 << 11,        // NT bf16: every groupable launch on the column-grouped walk (k-step schedule)
     VIPANT_SW_GROUPED_NEVER = 1 << 12,         // NT bf16: no launch on the column-grouped walk
     VIPANT_SW_E4M3_KSTEP = 1 << 15,            // NT e4m3, plain epilogue: the k-step schedule instead of DEEP
