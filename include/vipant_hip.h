@@ -320,6 +320,32 @@ int32_t vipant_infonce_fwd_bwd(const float* x1, const float* x2, const float* lo
                                int64_t B, int64_t E, int64_t row0, int64_t nrows, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* ---- Several InfoNCE terms over shared operands (VACELossHead.forward, cvap/module/decoder/loss_head.py:572-598) ----
+ * x: HOST table of nop <= 5 device matrices, fp32 [B, E], L2-normalised.  pair_a / pair_b: HOST tables of npair <= 5 operand indices,
+ * a_k != b_k; pair k is vipant_infonce_fwd_bwd(x[a_k], x[b_k]) with the raw logit_scale[k] (DEVICE, [npair]) and the HOST values
+ * scale_max[k] (<= 0: none) and weight[k].
+ *   loss[k]          (DEVICE, [npair + 1]) the unweighted loss of pair k, the single-pair call's; loss[npair] = sum_k weight[k] loss[k],
+ *                    summed in ascending k on the device;
+ *   dx[i]            (HOST table of device pointers; the table or an entry may be NULL: no gradient for that operand) fp32 [nrows, E]
+ *                    = grad_scale * sum_{k with i in pair k} weight[k] * dloss_k/dx_i for the rows [row0, row0 + nrows): written in
+ *                    full, summed in ascending k, no atomics -- the same bits on every call;
+ *   dlogit_scale[k]  (DEVICE, [npair], or NULL) = weight[k] * grad_scale * dloss_k/dlogit_scale_k, 0 where the clamp is active.
+ * Refused with VIPANT_EBADSHAPE before anything is written: an operand with a gradient pointer that is in no pair, an index out of
+ * range, a_k == b_k, nop or npair outside 1 .. 5, E % 64 != 0.
+ * B <= 768 at E = 512 (the step's own batch): three launches whatever the pair count -- one split / transpose of every operand, one
+ * log-sum-exp launch over all (pair, side), one gradient launch whose workgroups own (operand, 16 rows, 128 columns) and walk the
+ * operand's pairs with s_k w_k dZ_k as the bf16 MFMA operand into ONE set of accumulators.  npair = 1, weight 1 gives the bits of
+ * vipant_infonce_fwd_bwd.  Every other shape: the pairs one after another through vipant_infonce_fwd_bwd into workspace temporaries,
+ * added into dx in ascending k.  No allocation and no synchronisation in the call.
+ * Workspace: vipant_infonce_multi_workspace_bytes(B, E, nop, npair, nrows) is enough for any gradient table; the nrows = 0 size is
+ * enough for a call that produces no feature gradient (nrows = 0, or no gradient pointer). */
+size_t vipant_infonce_multi_workspace_bytes(int64_t B, int64_t E, int32_t nop, int32_t npair, int64_t nrows);
+int32_t vipant_infonce_multi_fwd_bwd(const float* const* x, int32_t nop, const int32_t* pair_a, const int32_t* pair_b,
+                                     int32_t npair, const float* logit_scale, const float* scale_max, const float* weight,
+                                     float* loss, float* const* dx, float* dlogit_scale, float grad_scale, int64_t B,
+                                     int64_t E, int64_t row0, int64_t nrows, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+
 /* ---- Retrieval evaluation (LossHead.report / retrieval_eval, cvap/module/decoder/loss_head.py:71-168) ----
  * x1 fp32 [N1, E] queries, x2 fp32 [N2, E] candidates (both L2-normalised by the caller), gold int32 [N1, G]
  * with entries in [0, N2).  Replaces `(x1 @ x2.t()).argsort(descending=True)` + `torch.where(ind == label)`:

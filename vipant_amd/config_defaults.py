@@ -37,6 +37,12 @@ GROUPS = {
             "data_name": "src_unbalanced_train_segments", "eval_name": "src_balanced_train_segments", "test_name": "",
             "eval_samples": 5184, "batch_size": 432, "multi_view": False, "siamese": dict(_siamese),
         }),
+        # configs/running/siamese.yaml (the multi-view VA trainer: worker=CVASP monitor=VASMonitor +model/loss=ce_va)
+        "siamese": dict(_running_common, **{
+            "data_name": "npz_unbalanced_train_segments", "eval_name": "npz_balanced_train_segments", "test_name": "eval",
+            "eval_samples": 5184, "save_rate": 300, "batch_size": 432, "save_epoch": False, "multi_view": True, "clip_tf": False,
+            "siamese": dict(_siamese),
+        }),
         "trimodal": dict(_running_common, **{
             "prompt": "the sound of", "cat_label": False, "filter_set": None, "label_map": "ontology,eval_segments",
             "data_name": "", "eval_name": "", "test_name": "", "eval_samples": 250, "test_samples": 250,
@@ -103,6 +109,10 @@ GROUPS = {
         "ce": {"name": "CELossHead", "layers": [], "scaling": True, "scale_max": None},
         "ce_val": {"name": "VALCELossHead", "layers": [], "scaling": True, "scale_max": None,
                    "va": True, "lv": False, "al": True},
+        # configs/model/loss/ce_va.yaml: v = image view 1, p = the precomputed ("prime") image features, a = audio
+        "ce_va": {"name": "VACELossHead", "layers": [], "scaling": True, "scale_max": None,
+                  "vp": True, "vp_w": 1., "ap": False, "ap_w": 1., "va": True, "va_w": 1., "vv": True, "vv_w": 1.,
+                  "aa": False, "aa_w": 1.},
         "barlow": {"name": "BarlowLossHead", "embed_dim": "${model.image.embed_dim}", "lambd_off": 0.0051,
                    "layers": [2048, 4096, 4096]},
         # `ce` carries only `name`, as in the reference's file: BarlowCELossHead fills scaling / scale_max from `ce` (logged)

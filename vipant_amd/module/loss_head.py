@@ -273,6 +273,85 @@ class VALCELossHead(LossHead):
         return loss
 
 
+@LOSS_HEADS_REGISTRY.register()
+class VACELossHead(LossHead):
+    """Up to five weighted InfoNCE terms over {prime image features, two image views, two audio views}
+    (cvap/module/decoder/loss_head.py:498-598).  Sub-heads `loss_head_{vp,ap,va,vv,aa}` are CELossHeads as in the reference (its
+    state dict loads strictly); they own the temperatures and the eval caches.  The training forward is ONE ops.InfoNCEMultiFn node
+    over the live operands and pairs: every operand is prepared once and its gradient is summed over its pairs inside the kernel;
+    under replicas with global negatives all live operands travel in one all-gather."""
+
+    # (key, first argument, second argument) of each sub-head's call, in the reference's order; operands by forward()'s names
+    PAIRS = (("vp", "images_v1", "images"), ("ap", "audios_v1", "images"), ("va", "images_v1", "audios_v1"),
+             ("vv", "images_v1", "images_v2"), ("aa", "audios_v1", "audios_v2"))
+
+    def __init__(self, cfg, **kwargs):
+        super().__init__()
+        self._total_loss = {}
+        for key, _, _ in self.PAIRS:
+            on = bool(getattr(cfg, key))
+            setattr(self, f"loss_head_{key}", CELossHead(cfg, **kwargs) if on else None)
+            if on:
+                self._total_loss[key] = 0.
+        self.vp_w, self.ap_w, self.va_w, self.vv_w, self.aa_w = cfg.vp_w, cfg.ap_w, cfg.va_w, cfg.vv_w, cfg.aa_w
+        self.negatives = kwargs.get("negatives", "global")
+
+    def copy_state_dict(self, state_dict):
+        pass
+
+    def _live(self, operands):
+        """[(key, sub-head, name of x1, name of x2)] of the terms whose head exists and whose two operands are given."""
+        return [(key, getattr(self, f"loss_head_{key}"), a, b) for key, a, b in self.PAIRS
+                if getattr(self, f"loss_head_{key}") is not None and operands[a] is not None and operands[b] is not None]
+
+    def infer(self, images, images_v1, audios_v1, images_v2=None, audios_v2=None, *args, **kwargs):
+        operands = dict(images=images, images_v1=images_v1, audios_v1=audios_v1, images_v2=images_v2, audios_v2=audios_v2)
+        for _, head, a, b in self._live(operands):
+            head.infer(operands[a], operands[b], *args, **kwargs)
+        return 0.
+
+    def stats(self, nstep=1, **kwargs):
+        return " ".join(f"{k} {float(v) / nstep:.3f}" for k, v in self._total_loss.items())
+
+    def report(self, gold_file=None):
+        out = []
+        for key, _, _ in self.PAIRS:
+            head = getattr(self, f"loss_head_{key}")
+            if head is not None and hasattr(head, "x1s"):
+                out.append(f"{key.upper()}: " + head.report(gold_file))
+        return "\n" + "\n".join(out).strip()
+
+    def forward(self, images, images_v1, audios_v1, images_v2=None, audios_v2=None, *args, **kwargs):
+        if not self.training:
+            if not dist.is_initialized() or dist.get_rank() == 0:
+                return self.infer(images, images_v1, audios_v1, images_v2=images_v2, audios_v2=audios_v2, *args, **kwargs)
+            return None
+        operands = dict(images=images, images_v1=images_v1, audios_v1=audios_v1, images_v2=images_v2, audios_v2=audios_v2)
+        live = self._live(operands)
+        if not live:
+            return 0.
+        names = [n for n in operands if any(n in (a, b) for _, _, a, b in live)]
+        xs = [operands[n] for n in names]
+        if not kwargs.get("normalized", False):
+            xs = [ops.L2NormFn.apply(x) for x in xs]
+        b = xs[0].shape[0]
+        row0, grad_scale = 0, 1.0
+        if parallel.active() and self.negatives == "global":
+            xs = parallel.all_gather_features(*xs)
+            row0 = parallel.rank() * b
+        elif parallel.active():
+            grad_scale = 1.0 / parallel.world_size()
+        heads = [head for _, head, _, _ in live]
+        scales = [h.logit_scale if isinstance(h.logit_scale, nn.Parameter) else h.logit_scale.to(xs[0].device) for h in heads]
+        meta = ops.InfoNCEMultiMeta([(names.index(a), names.index(b)) for _, _, a, b in live],
+                                    [0.0 if h.scale_max == float("inf") else float(h.scale_max) for h in heads],
+                                    [getattr(self, f"{key}_w") for key, _, _, _ in live], row0, b, grad_scale)
+        loss = ops.InfoNCEMultiFn.apply(meta, *xs, *scales)
+        for k, (key, _, _, _) in enumerate(live):
+            self._total_loss[key] += meta.losses[k]
+        return loss
+
+
 def _need_image_features(head, x1):
     if x1 is None:
         raise VipantError(f"{head}: the Barlow heads need image features (x1); with dummy images (the AT script, "

@@ -32,7 +32,10 @@ class SyntheticLoader:
     cvap/monitor/cvalp.py:136-154): (images, audios [b, T, F], text [b, L] i64, labels, names).  Seeded per rank and
     per step, reproducible.  `running.dp_chunk` (set by train.py for `mode=dp` under N replicas): the loader
     stands for the reference's ONE loader whose batch data_parallel scatters -- every replica draws the same global batch of
-    N x batch_size samples and keeps its contiguous chunk."""
+    N x batch_size samples and keeps its contiguous chunk.
+    `running.multi_view` (configs/running/siamese.yaml): the five-slot batch of the siamese VA trainer instead -- (prime image
+    features [b, E], image view 1, image view 2 [b, 3, res, res], audio view 1, audio view 2 [b, T, F], names); the two views of a
+    modality are one clip under independent noise."""
 
     def __init__(self, cfg, steps, with_text, device_rank=0):
         self.cfg, self.steps, self.with_text, self.rank = cfg, int(steps), with_text, device_rank
@@ -46,6 +49,7 @@ class SyntheticLoader:
         self.precomputed = bool(rcfg.get("precomputed_image", False)) or rcfg.get("frame_emb", None) is not None
         self.res = int(cfg.running.resolution) if not isinstance(cfg.running.resolution, (list, tuple)) else 224
         self.embed = int(cfg.running.embed_dim)
+        self.multi_view = bool(rcfg.get("multi_view", False))
 
     def __len__(self):
         return self.steps
@@ -54,6 +58,17 @@ class SyntheticLoader:
         for step in range(self.steps):
             g = torch.Generator().manual_seed(1213 + 1000 * self.rank + step)
             audios = torch.randn(self.b, self.T, self.F, generator=g)
+            if self.multi_view:
+                frames = torch.randn(self.b, 3, self.res, self.res, generator=g)
+                batch = (torch.randn(self.b, self.embed, generator=g),
+                         frames + 0.5 * torch.randn(frames.shape, generator=g), frames + 0.5 * torch.randn(frames.shape, generator=g),
+                         audios + 0.5 * torch.randn(audios.shape, generator=g), audios + 0.5 * torch.randn(audios.shape, generator=g))
+                names = [f"synthetic-{self.rank}-{step}-{i}" for i in range(self.b)]
+                if self.chunk is not None:
+                    sl = slice(self.chunk[0] * self.chunk[1], (self.chunk[0] + 1) * self.chunk[1])
+                    batch, names = tuple(t[sl] for t in batch), names[sl]
+                yield (*batch, names)
+                continue
             if self.with_text:
                 images = torch.zeros(self.b, 1, 1, 1)
                 lens = torch.randint(8, 78, (self.b,), generator=g)
@@ -120,6 +135,7 @@ class Monitor(object):
             if head is not None and hasattr(head, "encoder"):
                 head.encoder.stream_f16 = stream_f16
                 head.encoder.last_block_rows = last_rows
+        # (audio tower only: a trainable image tower -- worker=CVASP, model.image.freeze=False -- runs bf16 operands)
         if cfg.running.get("fp8_gemm", False):      # BASELINE.json configs[4]: e4m3 operands in the audio tower's NT contractions
             if model.audio_head is not None and hasattr(model.audio_head, "encoder"):
                 model.audio_head.encoder.fp8 = True
@@ -222,8 +238,17 @@ class Monitor(object):
             loss = self._forward_backward_micro(images, audios, text if self.with_text else None, mb)
         else:
             loss = self.model(images, audios, text if self.with_text else None)
-            from . import ops
-            loss.backward(gradient=ops.unit_grad(loss.device) if loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32 else None)
+            self._backward(loss)
+        self._reduce_and_update()
+        return loss
+
+    @staticmethod
+    def _backward(loss):
+        from . import ops
+        loss.backward(gradient=ops.unit_grad(loss.device) if loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32 else None)
+
+    def _reduce_and_update(self):
+        """(replica gradient reduction) -> optimizer: the tail of every step."""
         if self.grad_sync is not None:
             micro = getattr(self, "_micro_step", False)         # micro-batched step: nothing went through a per-block bucket
             self._micro_step = False
@@ -234,7 +259,11 @@ class Monitor(object):
             self.grad_sync.reduce_params(rest)      # one more bucket behind the per-block ones already in flight
             self.grad_sync.wait()
         self.optimizer.step()
-        return loss
+
+    def _step_inputs(self, batch):
+        """What `make_batch` returned -> (the arguments of `step`, the number of samples in the batch)."""
+        images, audios, text, _, _ = batch
+        return (images, audios, text), images.shape[0]
 
     # ------------------------------------------------------------------ cvalp.py:172-272
     def epoch(self, iepoch):
@@ -244,7 +273,7 @@ class Monitor(object):
         ocfg = self.cfg.optimizer
         warmup_step_rate = max(int(ocfg.warmup_steps) // 20, 1)      # cvalp.py:177
         for step, batch in enumerate(self.dataloader, start=iepoch * len(self.dataloader)):
-            images, audios, text, _, _ = self.make_batch(batch)
+            inputs, ninst = self._step_inputs(self.make_batch(batch))
             self.timeit(all_time, key="data")
             if ocfg.use_lars:
                 adjust_learning_rate(ocfg, self.optimizer, self.dataloader, step)
@@ -256,13 +285,13 @@ class Monitor(object):
                     param_group["lr"] = ratio * param_group["initial_lr"]
                 lrs = " ".join(f"{g['lr']:.2e}" for g in self.optimizer.param_groups)
                 self.echo(f"warmup lr: {lrs} @ {self.total_step}")
-            loss = self.step(images, audios, text)
+            loss = self.step(*inputs)
             if not ocfg.use_lars and ocfg.batch_sch and not warmup:
                 self.scheduler.step()               # after all warm-up is completed (cvalp.py:207-209)
             self.timeit(all_time, key="model")
             self.total_step += 1
             self.total_loss += loss.detach()
-            self.total_inst += images.shape[0] * nchunk
+            self.total_inst += ninst * nchunk
             if self.cfg.rank <= 0 and self.total_step % self.cfg.running.peep_rate == 0:
                 lr_w = self.optimizer.param_groups[0]["lr"]
                 lr_b = self.optimizer.param_groups[1]["lr"]
@@ -364,6 +393,54 @@ class VALMonitor(Monitor):
 class VAMonitor(Monitor):
     """VA pre-training trainer (cvap/monitor/cvap.py:21)."""
     with_text = False
+
+
+class VASMonitor(Monitor):
+    """Siamese multi-view VA trainer (cvap/monitor/siamese_va.py:19-180; `monitor=VASMonitor worker=CVASP +running=siamese`).  The
+    epoch loop is the base trainer's; what differs is the batch -- five slots, of which only the views that a live pair of
+    `model.loss` reads are moved to the device, image views rescaled bilinearly to `running.resolution` -- and the worker's
+    signature."""
+    with_text = False
+
+    def make_batch(self, batch):
+        lcfg, res = self.cfg.model.loss, self.cfg.running.resolution
+
+        def to_dev(x):
+            return torch.as_tensor(x).to(self.device, non_blocking=True)
+
+        def scale_images(images):
+            if images.dim() != 2 and images.shape[-1] != res and list(images.shape[1:]) != [1, 1, 1]:
+                images = torch.nn.functional.interpolate(images, res, mode="bilinear", align_corners=False)
+            return images
+        images = to_dev(batch[0]) if lcfg.vp or lcfg.ap else None
+        images_v1 = scale_images(to_dev(batch[1]))
+        images_v2 = scale_images(to_dev(batch[2])) if lcfg.vv else None
+        audios_v1 = to_dev(batch[3]).unsqueeze(1)
+        audios_v2 = to_dev(batch[4]).unsqueeze(1) if lcfg.aa else None
+        return images, images_v1, images_v2, audios_v1, audios_v2, batch[-1]
+
+    def _step_inputs(self, batch):
+        images, images_v1, images_v2, audios_v1, audios_v2, _ = batch
+        return (images, images_v1, images_v2, audios_v1, audios_v2), (images if images is not None else audios_v1).shape[0]
+
+    def step(self, images, images_v1, images_v2, audios_v1, audios_v2):
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = self.model(images, images_v1, audios_v1, text_v1=None, images_v2=images_v2, audios_v2=audios_v2)
+        self._backward(loss)
+        self._reduce_and_update()
+        return loss
+
+    def infer(self, dataloader, samples=float("inf"), iepoch=0, gold_file=None):
+        nsample = 0
+        start_time = time.time()
+        for ibatch, batch in enumerate(dataloader):
+            if nsample >= samples:
+                break
+            images, images_v1, _, audios_v1, _, names = self.make_batch(batch)
+            self.model(images, images_v1, audios_v1, names=names)
+            nsample += (images if images is not None else audios_v1).shape[0]
+        self.echo(f"# sample {nsample}; {nsample / (time.time() - start_time):.2f} samples/s")
+        return self.model.report(gold_file=gold_file)
 
 
 class SyntheticFolds:
@@ -625,4 +702,4 @@ class ESCMonitor(Monitor):
         return f"{float(precision.group(1)):2.2f} for zero-shot classification."
 
 
-__all__ = ["Monitor", "VAMonitor", "VALMonitor", "ESCMonitor", "SyntheticLoader", "SyntheticFolds"]
+__all__ = ["Monitor", "VAMonitor", "VALMonitor", "VASMonitor", "ESCMonitor", "SyntheticLoader", "SyntheticFolds"]

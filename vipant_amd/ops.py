@@ -1180,6 +1180,81 @@ class InfoNCEFn(torch.autograd.Function):
                 (dls if unit else dls * dloss).reshape(ls_shape) if need[2] else None, None, None, None, None)
 
 
+class InfoNCEMultiMeta:
+    """The non-tensor arguments of InfoNCEMultiFn: `pairs` [(a, b)] indexes the operand list, `scale_max` / `weights` are per pair;
+    rows [row0, row0 + nrows) get gradients, pre-multiplied by `grad_scale` (InfoNCEFn's conventions).  After the forward
+    `losses` is the fp32 device vector [npair + 1]: the unweighted loss of each pair, then the weighted total."""
+
+    def __init__(self, pairs, scale_max, weights, row0, nrows, grad_scale=1.0):
+        self.pairs = [(int(a), int(b)) for a, b in pairs]
+        self.scale_max = [float(s or 0.0) for s in scale_max]
+        self.weights = [float(w) for w in weights]
+        if not (len(self.pairs) == len(self.scale_max) == len(self.weights)):
+            raise _ffi.VipantError("infonce_multi: pairs, scale_max and weights differ in length")
+        self.row0, self.nrows, self.grad_scale = int(row0), int(nrows), float(grad_scale)
+        self.losses = None
+
+
+class InfoNCEMultiFn(torch.autograd.Function):
+    """VACELossHead.forward (cvap/module/decoder/loss_head.py:572-598) as ONE node: sum_k w_k InfoNCE(x[a_k], x[b_k]) over L2-normalised
+    fp32 operands [B, E] that the pairs share.  `apply(meta, *operands, *logit_scales)`: len(meta.pairs) raw logit scales follow the
+    operands.  An operand that needs no gradient (precomputed features) gets none computed."""
+
+    @staticmethod
+    def forward(ctx, meta, *tensors):
+        npair = len(meta.pairs)
+        nop = len(tensors) - npair
+        xs = [t.contiguous() for t in tensors[:nop]]
+        for i, x in enumerate(xs):
+            _need(x, F32, f"infonce_multi.x[{i}]")
+            if x.shape != xs[0].shape or x.dim() != 2:
+                raise _ffi.VipantError(f"infonce_multi: operand {i} is {tuple(x.shape)}, operand 0 {tuple(xs[0].shape)}")
+        B, E = xs[0].shape
+        dev = xs[0].device
+        need = ctx.needs_input_grad[1:]
+        nrows = meta.nrows
+        want = any(need) and nrows > 0
+        wants = [want and need[i] and any(i in p for p in meta.pairs) for i in range(nop)]
+        nbytes = query("vipant_infonce_multi_workspace_bytes", B, E, nop, npair, nrows if want else 0)
+        if nbytes == 0:
+            raise _ffi.VipantError(f"infonce_multi: {nop} operands / {npair} pairs (1 to 5 each)")
+        ws = scratch("infonce_multi", nbytes, dev)
+        losses = torch.empty((npair + 1,), dtype=F32, device=dev)
+        dxs = [torch.empty((nrows, E), dtype=F32, device=dev) if w else None for w in wants]
+        dls = torch.empty((npair,), dtype=F32, device=dev) if want else None
+        ls = torch.stack([t.detach().reshape(()).to(F32) for t in tensors[nop:]])
+        ptrs = lambda ts: (C.c_void_p * len(ts))(*[_ptr(t) for t in ts])
+        i32s = lambda v: (C.c_int32 * len(v))(*v)
+        f32s = lambda v: (C.c_float * len(v))(*v)
+        call("vipant_infonce_multi_fwd_bwd", ptrs(xs), nop, i32s([a for a, _ in meta.pairs]), i32s([b for _, b in meta.pairs]), npair,
+             ls.data_ptr(), f32s(meta.scale_max), f32s(meta.weights), losses.data_ptr(), ptrs(dxs), _ptr(dls), meta.grad_scale,
+             B, E, meta.row0, nrows, ws.data_ptr(), ws.numel(), _stream())
+        meta.losses = losses
+        if want:
+            ctx.save_for_backward(dls, *[d for d in dxs if d is not None])
+            ctx.meta = (B, E, meta.row0, nrows, nop, [d is not None for d in dxs], [tuple(t.shape) for t in tensors[nop:]])
+        return losses[npair].reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dls, *have = ctx.saved_tensors
+        B, E, row0, nrows, nop, present, ls_shapes = ctx.meta
+        need = ctx.needs_input_grad[1:]
+        unit = dloss.dim() == 0 and dloss.data_ptr() == unit_grad(dloss.device).data_ptr()      # the trainer's cached 1.0
+        have = iter(have)
+        dxs = [next(have) if p else None for p in present]
+
+        def expand(d):
+            if row0 == 0 and nrows == B:         # one replica: the slice is the batch
+                return d if unit else d * dloss
+            full = torch.zeros((B, E), dtype=F32, device=d.device)
+            full[row0:row0 + nrows] = d * dloss
+            return full
+        dl = dls if unit else dls * dloss
+        return (None, *[expand(dxs[i]) if need[i] and dxs[i] is not None else None for i in range(nop)],
+                *[dl[k].reshape(s) if need[nop + k] else None for k, s in enumerate(ls_shapes)])
+
+
 # ---------------------------------------------------------------------------------- LARS
 class LarsState:
     """Device-side pointer tables for vipant_lars_step (cvap/module/lars.py:43-72); built once per optimizer.

@@ -70,11 +70,12 @@ class _AllGatherRows(torch.autograd.Function):
         return g[r * ctx.b:(r + 1) * ctx.b].contiguous()
 
 
-def all_gather_features(x1: torch.Tensor, x2: torch.Tensor):
-    """One collective for both modalities: gathers [b, 2E], returns the two [B, E] halves (contiguous)."""
-    E = x1.shape[1]
-    both = _AllGatherRows.apply(torch.cat([x1, x2], dim=1))
-    return both[:, :E].contiguous(), both[:, E:].contiguous()
+def all_gather_features(*xs: torch.Tensor):
+    """One collective for all feature blocks (the two modalities of a pair; every live operand of VACELossHead): gathers
+    [b, n E], returns the n [B, E] parts (contiguous)."""
+    E = xs[0].shape[1]
+    packed = _AllGatherRows.apply(torch.cat(xs, dim=1))
+    return tuple(packed[:, i * E:(i + 1) * E].contiguous() for i in range(len(xs)))
 
 
 class GradSync:
