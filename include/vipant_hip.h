@@ -372,6 +372,22 @@ int32_t vipant_fbank(const float* wave, int64_t wave_stride, const int64_t* nsam
                      int64_t b, int64_t T, int64_t F, int32_t window_size, int32_t window_shift, int32_t nfft,
                      float preemphasis, int32_t zero_mean, float norm_mean, float norm_std, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* vipant_fbank with waveform mixup inside the launch (cvap/data/audioset_cls.py:374-398; zero_mean is implied).  mix_index int32
+ * [b] = the partner clip IN THIS BATCH or -1 for "not mixed", mix_lambda fp32 [b]; both on the device.  With c_i = w_i - mean(w_i
+ * over nsamples[i]): an unmixed clip is c_i; a mixed one is x[j] = lambda c_i[j] + (1 - lambda) (j < nsamples[p] ? c_p[j] : 0) for
+ * j < nsamples[i] -- the partner truncated or zero-padded to the clip's length, always the ORIGINAL clip p, never its mixed
+ * version -- minus the mean of x over nsamples[i].  From there on the pipeline is vipant_fbank's.  The mixed waveform is never
+ * stored: the frame loader forms the samples from the two sources on the way into LDS; `workspace`
+ * (vipant_fbank_mix_workspace_bytes(b)) holds the per-clip means only.  The mean reductions are fixed-order, no float atomics: two
+ * runs are bit-identical, and a clip with mix_index -1 gets the bits of vipant_fbank(..., zero_mean = 1).  A mix_index outside
+ * [-1, b) cannot be seen by the host: the kernel clamps it into the range (below -1: not mixed; b and above: clip b - 1) before
+ * any use.  A NULL argument (masks excepted) or a bad shape is refused and nothing is written. */
+size_t vipant_fbank_mix_workspace_bytes(int64_t b);
+int32_t vipant_fbank_mix(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, const float* window,
+                         const float* banks, const int32_t* bank_start, const int32_t* bank_len, const int32_t* masks,
+                         const int32_t* mix_index, const float* mix_lambda, int64_t b, int64_t T, int64_t F,
+                         int32_t window_size, int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean,
+                         float norm_std, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- LARS (cvap/module/lars.py:43-72), one fused pass per tensor list ---------------------------------
  * For tensor i (n[i] elements): dp = g + wd*p (adapt[i]); q = eta*|p|/|dp| (adapt[i], both norms > 0);
@@ -425,7 +441,11 @@ int32_t vipant_barlow_loss(const float* c, int64_t ldc, int64_t M, float lambd, 
  * (optional) = arg-max column, the lowest index on exact ties (torch.argmax, loss_head.py:356-357).
  * vipant_bce_logits: nn.BCEWithLogitsLoss()(exp(ls) * z, targets), cvap/module/decoder/loss_more.py:66-69, 140-142, in the
  * overflow-safe max(x, 0) - x t + log1p(exp(-|x|)) form.  targets uint8 [B, ldt] (non-zero = 1); logit_scale may be NULL
- * (scale 1: `scaling: False`; dscale must then be NULL); prob fp32 [B, ldp] (optional) = sigmoid(exp(ls) * z). */
+ * (scale 1: `scaling: False`; dscale must then be NULL); prob fp32 [B, ldp] (optional) = sigmoid(exp(ls) * z).
+ * vipant_bce_logits_soft: the same against SOFT targets fp32 [B, ldt] (mixup's lambda y + (1 - lambda) y', audioset_cls.py:400);
+ * same arguments, same workspace (vipant_bce_logits_workspace_bytes).  dz = grad_scale * s * (sigmoid(x) - t) / (B C).  An
+ * element whose target is exactly 0 or 1 takes vipant_bce_logits' arithmetic, so float {0, 1} targets give its outputs bit for
+ * bit.  Targets outside [0, 1] are NOT clamped: the formula is evaluated as it stands. */
 size_t vipant_softmax_ce_workspace_bytes(int64_t nrows);
 int32_t vipant_softmax_ce(const float* z, int64_t ldz, const int64_t* labels, const float* logit_scale, float* loss, uint16_t* dz,
                           int64_t ldd, float* dscale, int32_t* pred, int64_t row0, int64_t nrows, float grad_scale, int64_t B,
@@ -434,6 +454,9 @@ size_t vipant_bce_logits_workspace_bytes(int64_t nrows);
 int32_t vipant_bce_logits(const float* z, int64_t ldz, const uint8_t* targets, int64_t ldt, const float* logit_scale, float* loss,
                           uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp, int64_t row0, int64_t nrows,
                           float grad_scale, int64_t B, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+int32_t vipant_bce_logits_soft(const float* z, int64_t ldz, const float* targets, int64_t ldt, const float* logit_scale, float* loss,
+                               uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp, int64_t row0, int64_t nrows,
+                               float grad_scale, int64_t B, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ==== The fused operator set: one entry point per reference operator group, forward and backward ==========
  * Host-side compositions of the kernels above (vipant_amd/csrc/block.hip): same stream, no allocation, no synchronisation.

@@ -98,6 +98,8 @@ PROTOTYPES = {
     "vipant_retrieval_ranks": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _sz, _p]),
     "vipant_fbank_workspace_bytes": (_sz, [_i64]),
     "vipant_fbank": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _f32, _f32, _p, _sz, _p]),
+    "vipant_fbank_mix_workspace_bytes": (_sz, [_i64]),
+    "vipant_fbank_mix": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _p, _sz, _p]),
     # fused operator set (vipant_amd/csrc/block.hip)
     "vipant_block_workspace_bytes": (_sz, [_i64, _i64]),
     "vipant_ln_qkv_fwd": (_i32, [_p] * 11 + [_i64, _i64, _p, _i32, _p]),
@@ -126,6 +128,7 @@ PROTOTYPES = {
     "vipant_softmax_ce": (_i32, [_p, _i64, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
     "vipant_bce_logits_workspace_bytes": (_sz, [_i64]),
     "vipant_bce_logits": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
+    "vipant_bce_logits_soft": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
 }
 
 

@@ -62,6 +62,18 @@ GROUPS = {
             "eval_samples": 5000, "test_samples": 5000, "peep_rate": 50, "save_rate": 1e9, "batch_size": 50, "epochs": 32,
             "save_epoch": True, "excl_modules": {"amodules": []}, "synthetic_folds": 2, "synthetic_classes": 10,
         }),
+        # AudioSet tagging (configs/running/audioset.yaml: worker=ASClassifier monitor=ASMonitor +model/loss=bce), key for key; the
+        # paths default to local, dataset-free operation like every group here.  `synthetic_*` / `sample_rate`: ASMonitor's seeded
+        # tagging loader -- waveforms of `synthetic_seconds` at `sample_rate` through the GPU front-end (`synthetic_wave`, which
+        # waveform mixup needs), or ready spectrograms as the reference collator yields them
+        "audioset": dict(_running_common, **{
+            "prompt": "the sound of", "cat_label": False, "nper_label": -1, "filter_set": None, "label_map": "ontology,eval_segments",
+            "data_name": "npz_train_toy", "eval_name": "npz_eval_toy", "test_name": "npz_eval_toy", "eval_samples": 250,
+            "test_samples": 250, "peep_rate": 1, "save_rate": 3, "batch_size": 64, "epochs": 1000, "save_epoch": False,
+            "force_npz": False, "zero_shot": False, "clf": True, "np_rnd": False, "imagine": False, "mixup_rate": 0.5,
+            "weighted_sampling": False, "excl_modules": {"vmodules": [], "amodules": [], "lmodules": []},
+            "synthetic_classes": 527, "synthetic_wave": True, "synthetic_seconds": 10.0, "sample_rate": 16000,
+        }),
     },
     "running/audio": {
         "default": {

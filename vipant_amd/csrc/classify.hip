@@ -143,7 +143,10 @@ __global__ __launch_bounds__(256) void softmax_ce_rows(const float* __restrict__
 
 // binary cross entropy with logits of x = s * z against t in {0, 1}: max(x, 0) - x t + log1p(exp(-|x|)), mean over B * C;
 // dz = g (sigmoid(x) - t), g = grad_scale * s / (B C); r = d / d logit_scale = sum (sigmoid(x) - t) x.
-__global__ __launch_bounds__(256) void bce_logits_rows(const float* __restrict__ z, int64_t ldz, const uint8_t* __restrict__ tg,
+// TG = uint8_t: binary targets (non-zero = 1).  TG = float: soft targets (mixup's lam y + (1 - lam) y'), not clamped; an element
+// whose target is exactly 0 or 1 takes the binary arithmetic, so float {0, 1} targets give the uint8 kernel's bits.
+template <typename TG>
+__global__ __launch_bounds__(256) void bce_logits_rows(const float* __restrict__ z, int64_t ldz, const TG* __restrict__ tg,
                                                        int64_t ldt, const float* __restrict__ logit_scale, bf16_t* __restrict__ dz,
                                                        int64_t ldd, float* __restrict__ prob, int64_t ldp, int row0, int nrows,
                                                        float grad_scale, float inv_bc, int C, float* __restrict__ part) {
@@ -155,15 +158,19 @@ __global__ __launch_bounds__(256) void bce_logits_rows(const float* __restrict__
         const float s = logit_scale != nullptr ? expf(logit_scale[0]) : 1.f;
         const float g = grad_scale * s * inv_bc;
         const float* zr = z + (int64_t)row * ldz;
-        const uint8_t* tr = tg + (int64_t)row * ldt;
+        const TG* tr = tg + (int64_t)row * ldt;
         bf16_t* drow = dz != nullptr ? dz + (int64_t)row * ldd : nullptr;
         float* prow = prob != nullptr ? prob + (int64_t)row * ldp : nullptr;
         for (int j = lane; j < C; j += 64) {
             const float x = s * zr[j];
-            const float t = tr[j] != 0 ? 1.f : 0.f;
+            float t;
+            if constexpr (sizeof(TG) == 1) t = tr[j] != 0 ? 1.f : 0.f;
+            else t = tr[j];
             const float e = expf(-fabsf(x));
             const float sg = (x >= 0.f ? 1.f : e) / (1.f + e);
-            const float q = t != 0.f ? -((x >= 0.f ? e : 1.f) / (1.f + e)) : sg;      // sigmoid(x) - t without cancellation
+            float q;
+            if constexpr (sizeof(TG) == 1) q = t != 0.f ? -((x >= 0.f ? e : 1.f) / (1.f + e)) : sg;      // sigmoid(x) - t without cancellation
+            else q = t == 1.f ? -((x >= 0.f ? e : 1.f) / (1.f + e)) : (t == 0.f ? sg : sg - t);
             loss += fmaxf(x, 0.f) - x * t + log1pf(e);
             dls = __builtin_fmaf(q, x, dls);
             if (drow != nullptr) drow[j] = f32_to_bf16(g * q);
@@ -247,24 +254,41 @@ extern "C" int32_t vipant_softmax_ce(const float* z, int64_t ldz, const int64_t*
     return VIPANT_OK;
 }
 
-extern "C" int32_t vipant_bce_logits(const float* z, int64_t ldz, const uint8_t* targets, int64_t ldt, const float* logit_scale,
-                                     float* loss, uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp, int64_t row0,
-                                     int64_t nrows, float grad_scale, int64_t B, int64_t C, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    int32_t rc = cls_check("bce_logits", ldz, ldd, dz != nullptr, row0, nrows, B, C, workspace, workspace_bytes);
+template <typename TG>
+static int32_t bce_launch(const char* who, const float* z, int64_t ldz, const TG* targets, int64_t ldt, const float* logit_scale,
+                          float* loss, uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp, int64_t row0,
+                          int64_t nrows, float grad_scale, int64_t B, int64_t C, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    int32_t rc = cls_check(who, ldz, ldd, dz != nullptr, row0, nrows, B, C, workspace, workspace_bytes);
     if (rc != VIPANT_OK) return rc;
     VIPANT_REQUIRE(z != nullptr && targets != nullptr && loss != nullptr && ldt >= C, VIPANT_EBADSHAPE,
-                   "bce_logits: z, targets and loss are required (ldt >= C)");
-    VIPANT_REQUIRE(prob == nullptr || ldp >= C, VIPANT_EBADSHAPE, "bce_logits: ldp=%ld is smaller than C=%ld", (long)ldp, (long)C);
-    VIPANT_REQUIRE(dscale == nullptr || logit_scale != nullptr, VIPANT_EBADSHAPE, "bce_logits: dscale needs logit_scale");
+                   "%s: z, targets and loss are required (ldt >= C)", who);
+    VIPANT_REQUIRE(prob == nullptr || ldp >= C, VIPANT_EBADSHAPE, "%s: ldp=%ld is smaller than C=%ld", who, (long)ldp, (long)C);
+    VIPANT_REQUIRE(dscale == nullptr || logit_scale != nullptr, VIPANT_EBADSHAPE, "%s: dscale needs logit_scale", who);
     hipStream_t s = (hipStream_t)stream;
     float* part = (float*)workspace;
     const unsigned groups = (unsigned)cls_groups(nrows);
     const double inv = 1.0 / ((double)B * (double)C);
-    hipLaunchKernelGGL(bce_logits_rows, dim3(groups), dim3(256), 0, s, z, ldz, targets, ldt, logit_scale, (bf16_t*)dz, ldd, prob, ldp,
-                       (int)row0, (int)nrows, grad_scale, (float)inv, (int)C, part);
+    hipLaunchKernelGGL(bce_logits_rows<TG>, dim3(groups), dim3(256), 0, s, z, ldz, targets, ldt, logit_scale, (bf16_t*)dz, ldd, prob,
+                       ldp, (int)row0, (int)nrows, grad_scale, (float)inv, (int)C, part);
     VIPANT_LAUNCH_CHECK();
     hipLaunchKernelGGL(cls_finish, dim3(1), dim3(256), 0, s, part, (int64_t)groups, inv, grad_scale, loss, dscale);
     VIPANT_LAUNCH_CHECK();
     return VIPANT_OK;
+}
+
+extern "C" int32_t vipant_bce_logits(const float* z, int64_t ldz, const uint8_t* targets, int64_t ldt, const float* logit_scale,
+                                     float* loss, uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp, int64_t row0,
+                                     int64_t nrows, float grad_scale, int64_t B, int64_t C, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    return bce_launch<uint8_t>("bce_logits", z, ldz, targets, ldt, logit_scale, loss, dz, ldd, dscale, prob, ldp, row0, nrows, grad_scale,
+                               B, C, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t vipant_bce_logits_soft(const float* z, int64_t ldz, const float* targets, int64_t ldt, const float* logit_scale,
+                                          float* loss, uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp,
+                                          int64_t row0, int64_t nrows, float grad_scale, int64_t B, int64_t C, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    return bce_launch<float>("bce_logits_soft", z, ldz, targets, ldt, logit_scale, loss, dz, ldd, dscale, prob, ldp, row0, nrows,
+                             grad_scale, B, C, workspace, workspace_bytes, stream);
 }

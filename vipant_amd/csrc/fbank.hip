@@ -20,6 +20,7 @@ struct FbankArgs {
     const float* wave; int64_t wave_stride; const int64_t* nsamples; float* out;
     const float* window; const float* banks; const int32_t* bank_start; const int32_t* bank_len; const int32_t* masks;
     const float* clip_mean;
+    const int32_t* mix_index; const float* mix_lambda; const float* mix_mean;      // vipant_fbank_mix only
     int T, F, size, shift;
     float preemph, norm_mean, norm_std;
 };
@@ -41,6 +42,52 @@ __global__ __launch_bounds__(256) void clip_mean_kernel(const float* __restrict_
     if (threadIdx.x == 0) mean[clip] = n > 0 ? red[0] / (float)n : 0.f;
 }
 
+// the partner of a clip: mix_index clamped into [-1, b) -- the host cannot see a device array's values
+__device__ __forceinline__ int mix_partner(const int32_t* __restrict__ mix_index, int clip, int b) {
+    const int p = mix_index[clip];
+    return p < 0 ? -1 : (p >= b ? b - 1 : p);
+}
+
+// mixup on the waveform (cvap/data/audioset_cls.py:374-398): mean over nsamples[i] of x = lam c_i + (1 - lam) c_p, c = w - mean(w),
+// the partner truncated or zero-padded to the clip's length.  One workgroup per clip; a clip is 640 KB at 10 s, so the pass is
+// bound by how many loads one CU keeps in flight: 1024 threads, four independent strided partial sums each, then an LDS tree --
+// a fixed order, no atomics.
+constexpr int MIX_MEAN_THREADS = 1024;
+
+__global__ __launch_bounds__(MIX_MEAN_THREADS) void mix_mean_kernel(const float* __restrict__ wave, int64_t stride,
+                                                                    const int64_t* __restrict__ nsamples,
+                                                                    const int32_t* __restrict__ mix_index,
+                                                                    const float* __restrict__ mix_lambda,
+                                                                    const float* __restrict__ mean, float* __restrict__ mix_mean) {
+    constexpr int NT = MIX_MEAN_THREADS;
+    __shared__ float red[NT];
+    const int clip = blockIdx.x;
+    const int p = mix_partner(mix_index, clip, (int)gridDim.x);
+    if (p < 0) {                                                  // uniform over the workgroup
+        if (threadIdx.x == 0) mix_mean[clip] = 0.f;
+        return;
+    }
+    const int64_t n = nsamples[clip];
+    const int64_t np = nsamples[p] < stride ? nsamples[p] : stride;
+    const float* w = wave + (int64_t)clip * stride;
+    const float* wp = wave + (int64_t)p * stride;
+    const float lam = mix_lambda[clip], oml = 1.f - lam, m = mean[clip], mp = mean[p];
+    auto x = [&](int64_t i) { return lam * (w[i] - m) + oml * (i < np ? wp[i] - mp : 0.f); };
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int64_t i = threadIdx.x;
+    for (; i + 3 * NT < n; i += 4 * NT) {
+        s0 += x(i); s1 += x(i + NT); s2 += x(i + 2 * NT); s3 += x(i + 3 * NT);
+    }
+    for (; i < n; i += NT) s0 += x(i);
+    red[threadIdx.x] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    for (int o = NT / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) mix_mean[clip] = n > 0 ? red[0] / (float)n : 0.f;
+}
+
 // LDS traffic of one wave is processed in program order, and a frame is private to its wave: between FFT passes it is
 // enough to stop the compiler from moving LDS accesses across the pass boundary.
 __device__ __forceinline__ void wave_lds_sync() {
@@ -53,7 +100,8 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 w) { return make_float2(
 constexpr int FPW = 4;            // frame PAIRS per wave: the workgroup's tables (twiddles, window, mel weights) serve 32 frames
 constexpr int MAXF = 256;         // mel bins
 
-template <int NFFT>
+// MIX: a clip with a partner forms its samples from two sources on the way into LDS (the mixed waveform is never stored)
+template <int NFFT, bool MIX>
 __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_off[MAXF + 1], s_start[MAXF], s_len[MAXF];
@@ -97,6 +145,17 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     const int32_t* mk = a.masks != nullptr ? a.masks + (int64_t)clip * 4 : nullptr;
     int f0 = 0, f1 = 0, t0 = 0, t1 = 0;
     if (mk != nullptr) { f0 = mk[0]; f1 = mk[1]; t0 = mk[2]; t1 = mk[3]; }
+    int partner = -1;
+    int64_t np = 0;
+    float lam = 1.f, oml = 0.f, pmean = 0.f, xmean = 0.f;
+    if constexpr (MIX) {
+        partner = mix_partner(a.mix_index, clip, (int)gridDim.y);
+        if (partner >= 0) {
+            np = a.nsamples[partner] < a.wave_stride ? a.nsamples[partner] : a.wave_stride;
+            lam = a.mix_lambda[clip]; oml = 1.f - lam;
+            pmean = a.clip_mean[partner]; xmean = a.mix_mean[clip];
+        }
+    }
 
     // Two real frames share one complex transform: z = y_a + i y_b, and with Z = FFT(z)
     //   X_a[k] = (Z[k] + conj Z[N-k]) / 2,   X_b[k] = (Z[k] - conj Z[N-k]) / (2i)
@@ -121,11 +180,19 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
         }
         if (!live_a && !live_b) continue;
         const float* src = a.wave + (int64_t)clip * a.wave_stride + (int64_t)ta * a.shift;
+        const float* psrc = a.wave + (int64_t)(partner >= 0 ? partner : clip) * a.wave_stride;
         float* raw_b = raw + NFFT;
         float sa = 0.f, sb = 0.f;
         for (int j = lane; j < a.size; j += 64) {
-            const float xa = live_a ? src[j] - cmean : 0.f;
-            const float xb = live_b ? src[j + a.shift] - cmean : 0.f;
+            float xa = live_a ? src[j] - cmean : 0.f;
+            float xb = live_b ? src[j + a.shift] - cmean : 0.f;
+            if constexpr (MIX) {
+                if (partner >= 0) {                               // the ORIGINAL partner clip, truncated / zero-padded to this clip
+                    const int64_t ja = (int64_t)ta * a.shift + j, jb = ja + a.shift;
+                    if (live_a) xa = (lam * xa + oml * (ja < np ? psrc[ja] - pmean : 0.f)) - xmean;
+                    if (live_b) xb = (lam * xb + oml * (jb < np ? psrc[jb] - pmean : 0.f)) - xmean;
+                }
+            }
             raw[j] = xa; raw_b[j] = xb;
             sa += xa; sb += xb;
         }
@@ -209,15 +276,15 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     }
 }
 
-template <int NFFT>
+template <int NFFT, bool MIX>
 int32_t launch_fbank(const FbankArgs& a, int64_t b, hipStream_t s) {
     static DeviceOnce once;
     const size_t lds = ((size_t)4 * 2 * NFFT + NFFT / 2) * sizeof(float2) + (size_t)2 * NFFT * sizeof(float);
     if (first_on_device(once)) {
-        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)fbank_kernel<NFFT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)fbank_kernel<NFFT, MIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         done_on_device(once);
     }
-    hipLaunchKernelGGL(fbank_kernel<NFFT>, dim3((unsigned)((a.T + 8 * FPW - 1) / (8 * FPW)), (unsigned)b), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((fbank_kernel<NFFT, MIX>), dim3((unsigned)((a.T + 8 * FPW - 1) / (8 * FPW)), (unsigned)b), dim3(256), lds, s, a);
     VIPANT_LAUNCH_CHECK();
     return VIPANT_OK;
 }
@@ -246,11 +313,44 @@ extern "C" int32_t vipant_fbank(const float* wave, int64_t wave_stride, const in
         hipLaunchKernelGGL(clip_mean_kernel, dim3((unsigned)b), dim3(256), 0, s, wave, wave_stride, nsamples, cmean);
         VIPANT_LAUNCH_CHECK();
     }
-    FbankArgs a{wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, cmean,
+    FbankArgs a{wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, cmean, nullptr, nullptr, nullptr,
                 (int)T, (int)F, window_size, window_shift, preemphasis, norm_mean, norm_std};
     switch (nfft) {
-        case 512: return launch_fbank<512>(a, b, s);
-        case 1024: return launch_fbank<1024>(a, b, s);
-        default: return launch_fbank<2048>(a, b, s);
+        case 512: return launch_fbank<512, false>(a, b, s);
+        case 1024: return launch_fbank<1024, false>(a, b, s);
+        default: return launch_fbank<2048, false>(a, b, s);
+    }
+}
+
+// per-clip means only: mean(w_i) and the mean of the mixed clip, b floats each
+extern "C" size_t vipant_fbank_mix_workspace_bytes(int64_t b) { return (size_t)((b * 8 + 255) / 256 * 256); }
+
+extern "C" int32_t vipant_fbank_mix(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, const float* window,
+                                    const float* banks, const int32_t* bank_start, const int32_t* bank_len, const int32_t* masks,
+                                    const int32_t* mix_index, const float* mix_lambda, int64_t b, int64_t T, int64_t F,
+                                    int32_t window_size, int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean,
+                                    float norm_std, void* workspace, size_t workspace_bytes, void* stream) {
+    VIPANT_REQUIRE(b > 0 && b < 65536 && T > 0 && F > 0 && F <= 256, VIPANT_EBADSHAPE, "fbank_mix: bad batch b=%ld T=%ld F=%ld", (long)b, (long)T, (long)F);
+    VIPANT_REQUIRE(nfft == 512 || nfft == 1024 || nfft == 2048, VIPANT_EBADSHAPE, "fbank_mix: padded window %d not in {512, 1024, 2048}", nfft);
+    VIPANT_REQUIRE(window_size > 1 && window_size <= nfft && window_size > nfft / 2 && window_shift > 0, VIPANT_EBADSHAPE,
+                   "fbank_mix: bad window %d / shift %d for padded size %d", window_size, window_shift, nfft);
+    VIPANT_REQUIRE(wave != nullptr && nsamples != nullptr && out != nullptr && window != nullptr && banks != nullptr &&
+                       bank_start != nullptr && bank_len != nullptr && mix_index != nullptr && mix_lambda != nullptr,
+                   VIPANT_EBADSHAPE, "fbank_mix: null argument");
+    VIPANT_REQUIRE(workspace != nullptr && workspace_bytes >= vipant_fbank_mix_workspace_bytes(b), VIPANT_ENOWORKSPACE,
+                   "fbank_mix: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    float* cmean = (float*)workspace;
+    float* xmean = cmean + b;
+    hipLaunchKernelGGL(clip_mean_kernel, dim3((unsigned)b), dim3(256), 0, s, wave, wave_stride, nsamples, cmean);
+    VIPANT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mix_mean_kernel, dim3((unsigned)b), dim3(MIX_MEAN_THREADS), 0, s, wave, wave_stride, nsamples, mix_index, mix_lambda, cmean, xmean);
+    VIPANT_LAUNCH_CHECK();
+    FbankArgs a{wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, cmean, mix_index, mix_lambda, xmean,
+                (int)T, (int)F, window_size, window_shift, preemphasis, norm_mean, norm_std};
+    switch (nfft) {
+        case 512: return launch_fbank<512, true>(a, b, s);
+        case 1024: return launch_fbank<1024, true>(a, b, s);
+        default: return launch_fbank<2048, true>(a, b, s);
     }
 }

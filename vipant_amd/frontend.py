@@ -3,7 +3,7 @@
 The reference computes one Kaldi filter bank per clip on CPU dataloader workers
 (cvap/data/audio/transform.py:12-35, parameters cvap/data/image_audio.py:119-126), pads / normalises it and applies
 SpecAugment masks (image_audio.py:183-207, configs/running/audio/default.yaml).  `KaldiFbank` does the same for a whole
-batch of device-resident waveforms in two launches (`vipant_fbank`) and returns the [b, 1, T, F] tensor
+batch of device-resident waveforms in two launches (`vipant_fbank`; three with waveform mixup, `vipant_fbank_mix`) and returns the [b, 1, T, F] tensor
 `ViTPreEncoder` takes.  File decoding, resampling and random cropping stay with the loader.
 
 The filter tables (Hann window, mel weights) are built once per (sample rate, bins) with torch ops on the device.
@@ -93,9 +93,27 @@ class KaldiFbank:
             rows.append(row)
         return torch.tensor(rows, dtype=torch.int32)
 
-    def __call__(self, wave: torch.Tensor, nsamples: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None):
+    @staticmethod
+    def draw_mixup(b: int, rate: float, generator: Optional[torch.Generator] = None):
+        """Mixup draws of one batch (cvap/data/audioset_cls.py:381-395, with the partner taken from the batch instead of the
+        dataset): per clip one uniform draw against `rate`, a partner uniform in [0, b), lambda ~ Beta(10, 10) as the ratio of two
+        Gamma(10) sums of exponentials.  -> (index int32 [b], -1 = not mixed; lambda fp32 [b], 1 where not mixed).  A clip that
+        draws itself stays unmixed.  Every clip consumes the same number of draws, mixed or not."""
+        u = torch.rand(b, generator=generator, dtype=torch.float64)
+        partner = torch.randint(0, max(b, 1), (b,), generator=generator)
+        e = -torch.log1p(-torch.rand(b, 20, generator=generator, dtype=torch.float64))      # Exp(1) draws; Gamma(10) = sum of 10
+        ga, gb = e[:, :10].sum(1), e[:, 10:].sum(1)
+        lam = (ga / (ga + gb)).to(F32)
+        mixed = (u < float(rate)) & (partner != torch.arange(b))
+        index = torch.where(mixed, partner, torch.full_like(partner, -1)).to(torch.int32)
+        return index, torch.where(mixed, lam, torch.ones_like(lam))
+
+    def __call__(self, wave: torch.Tensor, nsamples: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None,
+                 mix=None):
         """wave fp32 [b, n] on the device (rows zero-padded to a common n), nsamples int64 [b] valid lengths
-        (default: n), masks int32 [b, 4] or None  ->  [b, 1, max_len, num_mel_bins] fp32."""
+        (default: n), masks int32 [b, 4] or None  ->  [b, 1, max_len, num_mel_bins] fp32.
+        mix = (index int32 [b], lambda fp32 [b]) (draw_mixup): clip i becomes lambda c_i + (1 - lambda) c_index[i] on the
+        zero-mean waveforms, inside the launch (vipant_fbank_mix; zero_mean_wf is implied, as in the reference's clf loader)."""
         if not wave.is_cuda or wave.dtype != F32 or wave.dim() != 2:
             raise VipantError("fbank: wave must be a 2-d float32 device tensor (there is no CPU path)")
         wave = wave.contiguous()
@@ -107,8 +125,20 @@ class KaldiFbank:
         if masks is not None:
             masks = masks.to(device=dev, dtype=torch.int32).contiguous()
         out = torch.empty((b, 1, self.max_len, self.num_mel_bins), dtype=F32, device=dev)
-        ws = ops.scratch("fbank", query("vipant_fbank_workspace_bytes", b), dev)
         mean, std = self.norms if self.norms else (0.0, 0.0)
+        if mix is not None:
+            index = mix[0].to(device=dev, dtype=torch.int32).contiguous()
+            lam = mix[1].to(device=dev, dtype=F32).contiguous()
+            if index.shape != (b,) or lam.shape != (b,):
+                raise VipantError(f"fbank: mix index / lambda must have shape [{b}], got {tuple(index.shape)} / {tuple(lam.shape)}")
+            ws = ops.scratch("fbank", query("vipant_fbank_mix_workspace_bytes", b), dev)
+            call("vipant_fbank_mix", wave.data_ptr(), n, nsamples.data_ptr(), out.data_ptr(), self.window.data_ptr(),
+                 self.banks.data_ptr(), self.bank_start.data_ptr(), self.bank_len.data_ptr(),
+                 masks.data_ptr() if masks is not None else None, index.data_ptr(), lam.data_ptr(), b, self.max_len,
+                 self.num_mel_bins, self.size, self.shift, self.padded, self.preemphasis, float(mean), float(std), ws.data_ptr(),
+                 ws.numel(), ops._stream())
+            return out
+        ws = ops.scratch("fbank", query("vipant_fbank_workspace_bytes", b), dev)
         call("vipant_fbank", wave.data_ptr(), n, nsamples.data_ptr(), out.data_ptr(), self.window.data_ptr(),
              self.banks.data_ptr(), self.bank_start.data_ptr(), self.bank_len.data_ptr(),
              masks.data_ptr() if masks is not None else None, b, self.max_len, self.num_mel_bins, self.size, self.shift,

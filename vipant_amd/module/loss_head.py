@@ -472,6 +472,7 @@ class _ClassifierHead(LossHead):
     training forward through ops.ClassifierFn, the eval forward on rank 0 only."""
 
     kind = "ce"
+    soft_targets = False      # BCELossHead: floating-point targets are fractions (mixup), not multi-hot marks
 
     def _build_linear(self, sizes, last_bias=True):
         from .val import LayerNorm
@@ -500,6 +501,8 @@ class _ClassifierHead(LossHead):
         if self.kind == "ce":
             return torch.as_tensor(x2, device=device).long().contiguous()
         x2 = torch.as_tensor(x2, device=device)
+        if self.soft_targets and x2.is_floating_point():
+            return x2.float().contiguous()                                                      # mixup's fractional labels
         return (x2 if x2.dtype == torch.uint8 else (x2 != 0).to(torch.uint8)).contiguous()      # multi-hot: binary targets
 
     def _run(self, x1, x2, **meta_kwargs):
@@ -509,8 +512,10 @@ class _ClassifierHead(LossHead):
             params = [None if p is None else p.detach() for p in params]     # nothing will be differentiated: forward-only path
             ls = None if ls is None else ls.detach()
         grad_scale = 1.0 / parallel.world_size() if (parallel.active() and self.training) else 1.0
-        meta = ops.ClassifierMeta(self.kind, self.nclass, grad_scale, **meta_kwargs)
-        loss = ops.ClassifierFn.apply(x1.float(), self._target(x2, x1.device), ls, meta, *params)
+        target = self._target(x2, x1.device)
+        kind = "bce_soft" if (self.kind == "bce" and target.dtype == torch.float32) else self.kind
+        meta = ops.ClassifierMeta(kind, self.nclass, grad_scale, **meta_kwargs)
+        loss = ops.ClassifierFn.apply(x1.float(), target, ls, meta, *params)
         return loss, meta
 
     def forward(self, x1, x2, *args, **kwargs):
@@ -579,7 +584,10 @@ class BCELossHead(_ClassifierHead):
     """Multi-label tagging head (cvap/module/decoder/loss_more.py:29-143): `cfg.layers` hidden widths give LayerNorm / Linear
     pairs `linear.{2i}` / `linear.{2i+1}`, the last Linear has `bias=cfg.bias`; nn.BCEWithLogitsLoss on exp(logit_scale) x logits
     (`scaling: False`: a plain tensor of 0, scale 1).  Eval: `infer` returns the loss and caches the sigmoid scores; `report`
-    is the reference's string with its scikit-learn quantities restated in numpy (vipant_amd/util/metrics.py)."""
+    is the reference's string with its scikit-learn quantities restated in numpy (vipant_amd/util/metrics.py).
+    `soft_targets` (`cfg.soft_targets`, default False; ASMonitor sets it when `running.mixup_rate > 0`): floating-point targets
+    go to the soft-target kernel as fractions instead of being binarised; integer targets take the binary kernel either way.
+    The gold labels `infer` caches for `report` stay binary (evaluation data is never mixed)."""
 
     kind = "bce"
 
@@ -594,6 +602,7 @@ class BCELossHead(_ClassifierHead):
         self.logit_scale = (nn.Parameter(torch.ones([]) * np.log(1 / 0.07)) if cfg.scaling
                             else torch.ones([], requires_grad=False) * np.log(1 / 1))
         self.reduce = False
+        self.soft_targets = bool(getattr(cfg, "soft_targets", False))      # = cfg.get("soft_targets", False), for namespace configs too
 
     def copy_state_dict(self, state_dict):
         key = "logit_scale"
@@ -608,7 +617,8 @@ class BCELossHead(_ClassifierHead):
             loss, meta = self._run(x1.detach(), x2, want_prob=True)
         self.audios.append(x1.detach().float())
         self.x1s.append(meta.prob)
-        self.x2s.append(torch.as_tensor(x2, device=x1.device))
+        x2 = torch.as_tensor(x2, device=x1.device)
+        self.x2s.append((x2 != 0).to(x2.dtype) if (self.soft_targets and x2.is_floating_point()) else x2)
         names = kwargs.get("names", None)
         if names is not None:
             self.ids.extend(names)

@@ -91,8 +91,20 @@ class SyntheticLoader:
             yield images, audios, text, labels, names
 
 
+def _synthetic_prompts(seed, nclass):
+    """One tokenised prompt per class (`running.prompt` + label): SOT, ids, EOT, zero-padded to a common width."""
+    g = torch.Generator().manual_seed(seed)
+    prompts = []
+    for c in range(nclass):
+        n = int(torch.randint(3, 8, (1,), generator=g))
+        prompts.append([SOT] + torch.randint(1, SOT, (n,), generator=g).tolist() + [EOT])
+    width = max(len(t) for t in prompts)
+    return [t + [0] * (width - len(t)) for t in prompts]
+
+
 class Monitor(object):
     with_text = True      # VALMonitor (AT); VAMonitor sets False
+    partial_head_grads = False      # a classification head scores a rank's own rows: its gradients join the replica reduction
 
     def __init__(self, cfg, echo, device, dataloader=None):
         self.cfg, self.echo, self.device = cfg, echo, device
@@ -253,7 +265,8 @@ class Monitor(object):
             micro = getattr(self, "_micro_step", False)         # micro-batched step: nothing went through a per-block bucket
             self._micro_step = False
             rest = [p for p in self.params if micro or not getattr(p, "_vipant_bucketed", False)]
-            if self.model.loss_head is not None and self.cfg.running.get("negatives", "global") == "global":
+            if (not self.partial_head_grads and self.model.loss_head is not None
+                    and self.cfg.running.get("negatives", "global") == "global"):
                 skip = {id(p) for p in self.model.loss_head.parameters()}      # complete on every rank already
                 rest = [p for p in rest if id(p) not in skip]
             self.grad_sync.reduce_params(rest)      # one more bucket behind the per-block ones already in flight
@@ -486,13 +499,7 @@ class SyntheticFolds:
              (lambda k=k: (None, self._Loader(self, [k], b, False, (0, 1)))))
             for k in every]
         self.lid2str = [f"class {c}" for c in range(self.nclass)]
-        g = torch.Generator().manual_seed(self.seed + 1)
-        self.lid2int = []                       # one tokenised prompt per class (`running.prompt` + label): SOT, ids, EOT
-        for c in range(self.nclass):
-            n = int(torch.randint(3, 8, (1,), generator=g))
-            self.lid2int.append([SOT] + torch.randint(1, SOT, (n,), generator=g).tolist() + [EOT])
-        width = max(len(t) for t in self.lid2int)
-        self.lid2int = [t + [0] * (width - len(t)) for t in self.lid2int]
+        self.lid2int = _synthetic_prompts(self.seed + 1, self.nclass)
         self.label_map = None
 
     def batch(self, picks):
@@ -702,4 +709,177 @@ class ESCMonitor(Monitor):
         return f"{float(precision.group(1)):2.2f} for zero-shot classification."
 
 
-__all__ = ["Monitor", "VAMonitor", "VALMonitor", "VASMonitor", "ESCMonitor", "SyntheticLoader", "SyntheticFolds"]
+class SyntheticTagging:
+    """Seeded multi-label batches with the contract of the reference's AudioSet collator (cvap/data/audioset_cls.py):
+    (images, audios, text, multi-hot labels [b, C], names) with dummy [b, 1, 1, 1] images.  A clip has 1-3 positive classes and is
+    the sum of their prototypes plus noise.  `running.synthetic_wave=True`: the audio slot holds WAVEFORMS fp32 [b, n] -- a class
+    is a tone of its own frequency -- and the text slot their valid lengths int64 [b]; the trainer runs the GPU front-end on them
+    (waveform mixup needs the waveform).  False: spectrograms [b, T, F] as the reference collator yields them (a class is a
+    pattern over the mel bins).  Under replicas a rank draws its own batches."""
+
+    def __init__(self, cfg, steps, train, rank=0):
+        rcfg = cfg.running
+        self.steps, self.train, self.rank = int(steps), bool(train), int(rank)
+        self.b, self.nclass = int(rcfg.batch_size), int(rcfg.get("synthetic_classes", 527))
+        self.wave = bool(rcfg.get("synthetic_wave", True))
+        self.sr = float(rcfg.get("sample_rate", 16000))
+        self.n = int(self.sr * float(rcfg.get("synthetic_seconds", 10.0)))
+        self.T, self.F = int(rcfg.max_audio_len), int(rcfg.num_mel_bins)
+        self.seed = int(cfg.seed) + (0 if train else 500009)
+        g = torch.Generator().manual_seed(int(cfg.seed) + 2)
+        self.freq = 100.0 + (0.45 * self.sr - 100.0) * torch.rand(self.nclass, generator=g)      # Hz, below Nyquist
+        self.proto = torch.randn(self.nclass, self.F, generator=g)
+        self.lid2int = _synthetic_prompts(int(cfg.seed) + 1, self.nclass)
+
+    def __len__(self):
+        return self.steps
+
+    def __iter__(self):
+        for step in range(self.steps):
+            g = torch.Generator().manual_seed(self.seed + 1000 * self.rank + step)
+            labels = torch.zeros(self.b, self.nclass, dtype=torch.int64)
+            npos = torch.randint(1, 4, (self.b,), generator=g)
+            for i in range(self.b):
+                labels[i, torch.randperm(self.nclass, generator=g)[:int(npos[i])]] = 1
+            y = labels.float()
+            if self.wave:
+                t = torch.arange(self.n, dtype=torch.float32) / self.sr
+                phase = 2.0 * np.pi * torch.rand(self.b, self.nclass, generator=g)
+                audios = torch.zeros(self.b, self.n)
+                for i in range(self.b):
+                    for c in labels[i].nonzero().flatten().tolist():
+                        audios[i] += 0.1 * torch.sin(2.0 * np.pi * float(self.freq[c]) * t + float(phase[i, c]))
+                audios += 0.01 * torch.randn(self.b, self.n, generator=g)
+                text = torch.full((self.b,), self.n, dtype=torch.int64)
+            else:
+                audios = (y @ self.proto).unsqueeze(1) + torch.randn(self.b, self.T, self.F, generator=g)
+                text = torch.zeros(self.b, 1, dtype=torch.int64)
+            names = [f"synthetic-{'train' if self.train else 'eval'}-{self.rank}-{step}-{i}" for i in range(self.b)]
+            yield torch.zeros(self.b, 1, 1, 1), audios, text, labels, names
+
+
+class ASMonitor(Monitor):
+    """AudioSet tagging trainer (cvap/monitor/audioset_clf.py:25-467 without `eval_norms` and `repeated_zero_shot`;
+    `monitor=ASMonitor worker=ASClassifier +running=audioset +model/loss=bce`).  The epoch loop, schedules, peep line, periodic
+    eval and checkpoint are the base trainer's.  What differs is the batch: waveform batches go through the GPU front-end
+    (vipant_amd/frontend.py) inside `make_batch`, and when training with `running.mixup_rate > 0` the clips are mixed in the
+    front-end's launch with partners from the same batch (the reference draws the partner from the dataset in a loader worker)
+    and the labels become lam y + (1 - lam) y[partner], which BCELossHead scores as fractions (`soft_targets`).
+    `eval=True running.zero_shot=True` scores the clips against one prompt per class through the text tower."""
+    with_text = False
+    partial_head_grads = True
+
+    def __init__(self, cfg, echo, device, dataloader=None):
+        self.cfg, self.echo, self.device = cfg, echo, device
+        self.evalloader = self.testloader = None
+        self.gold_file = None
+        self.mixup_rate = float(cfg.running.get("mixup_rate", 0.0) or 0.0)
+        self.aug_generator = self._aug_generator()
+        self._fbank = {}
+        output_dim = self.build_data(dataloader)
+        model = build_main_model(cfg, echo)
+        tunable_params = model.build(output_dim=output_dim)
+        self.model = model
+        self._configure(model)
+        self.model.train(not cfg.eval)
+        self.model.loss_head.soft_targets = self.mixup_rate > 0
+        self.build_optimizer(tunable_params)
+
+    def _aug_generator(self):
+        """The host generator of the mixup and SpecAugment draws: seeded per rank, consumed in step order."""
+        return torch.Generator().manual_seed(int(self.cfg.seed) + 7 + 1000 * max(int(self.cfg.rank), 0))
+
+    def build_data(self, dataloader=None):
+        rcfg = self.cfg.running
+        steps, rank = int(rcfg.get("synthetic_steps", 8)), max(int(self.cfg.rank), 0)
+        evalloader = SyntheticTagging(self.cfg, steps, False, 0)
+        self.lid2int = evalloader.lid2int
+        if self.cfg.eval:
+            self.dataloader = dataloader if dataloader is not None else evalloader
+        else:
+            self.dataloader = dataloader if dataloader is not None else SyntheticTagging(self.cfg, steps, True, rank)
+            self.evalloader = evalloader if rcfg.eval_name else None
+        self.echo(f"Instantiate main dataloader from `synthetic': total {len(self.dataloader)} batches, "
+                  f"{evalloader.nclass} sound classes.")
+        return evalloader.nclass
+
+    def frontend(self, train):
+        from .frontend import KaldiFbank
+        if train not in self._fbank:
+            self._fbank[train] = KaldiFbank.from_config(self.cfg.running.audio, float(self.cfg.running.get("sample_rate", 16000)),
+                                                        train=train, device=self.device)
+        return self._fbank[train]
+
+    @staticmethod
+    def soft_labels(labels, index, lam):
+        """lam y + (1 - lam) y[partner] (audioset_cls.py:400); a clip without a partner (index -1, lam 1) keeps its labels exactly."""
+        y = labels.float()
+        index = index.to(y.device).long()
+        lam = lam.to(y.device).unsqueeze(1)
+        partner = torch.where(index < 0, torch.arange(y.shape[0], device=y.device), index)
+        return lam * y + (1.0 - lam) * y[partner]
+
+    # ------------------------------------------------------------------ audioset_clf.py:192-210
+    def make_batch(self, batch):
+        images = torch.as_tensor(batch[0]).to(self.device, non_blocking=True)
+        audios = torch.as_tensor(batch[1]).to(self.device, non_blocking=True)
+        labels = torch.as_tensor(batch[3]).to(self.device, non_blocking=True)
+        res = self.cfg.running.resolution
+        if images.dim() != 2 and images.shape[-1] != res and list(images.shape[1:]) != [1, 1, 1]:
+            images = torch.nn.functional.interpolate(images, res, mode="bilinear", align_corners=False)
+        if audios.dim() == 2:                                       # waveforms: log-mel, mixup and masks on the device
+            train = self.model.training
+            fbank = self.frontend(train)
+            nsamples = torch.as_tensor(batch[2]).to(self.device, non_blocking=True)
+            mix = None
+            if train and self.mixup_rate > 0:
+                mix = fbank.draw_mixup(audios.shape[0], self.mixup_rate, self.aug_generator)
+                labels = self.soft_labels(labels, *mix)
+            masks = fbank.draw_masks(audios.shape[0], self.aug_generator) if train else None
+            audios = fbank(audios.float(), nsamples, masks=masks, mix=mix)
+        else:
+            audios = audios.unsqueeze(1)
+        return images, audios, None, labels, batch[-1]
+
+    def _step_inputs(self, batch):
+        images, audios, _, labels, _ = batch
+        return (images, audios, labels), audios.shape[0]
+
+    def step(self, images, audios, labels):
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = self.model(images, audios, labels)
+        self._backward(loss)
+        self._reduce_and_update()
+        return loss
+
+    # ------------------------------------------------------------------ audioset_clf.py:147-175
+    def learn(self):
+        if not self.model.training and self.cfg.running.get("zero_shot", False):
+            self.echo("(Zero-shot) Evaluating started...")
+            with torch.no_grad():
+                report = self.zero_shot(self.dataloader, samples=self.cfg.running.eval_samples, gold_file=self.gold_file)
+            self.echo(f"{report}")
+            return None
+        return super().learn()
+
+    # ------------------------------------------------------------------ audioset_clf.py:334-404
+    def infer(self, dataloader, samples=float("inf"), iepoch=0, gold_file=None, **report_kwargs):
+        nsample = 0
+        start_time = time.time()
+        for ibatch, batch in enumerate(dataloader):
+            if nsample >= samples:
+                break
+            images, audios, _, labels, names = self.make_batch(batch)
+            self.model(images, audios, labels, names=names)
+            nsample += audios.shape[0]
+        self.echo(f"# sample {nsample}; {nsample / (time.time() - start_time):.2f} samples/s")
+        return self.model.report(gold_file=gold_file, **report_kwargs)
+
+    def zero_shot(self, dataloader, samples=float("inf"), iepoch=0, gold_file=None):
+        text = torch.cat([self.model.encode_text(torch.tensor(self.lid2int[s:s + 50], device=self.device))
+                          for s in range(0, len(self.lid2int), 50)])
+        return self.infer(dataloader, samples=samples, iepoch=iepoch, gold_file=gold_file, text=text)
+
+
+__all__ = ["Monitor", "VAMonitor", "VALMonitor", "VASMonitor", "ESCMonitor", "ASMonitor", "SyntheticLoader", "SyntheticFolds",
+           "SyntheticTagging"]

@@ -1491,6 +1491,19 @@ def bce_logits(z: torch.Tensor, targets: torch.Tensor, logit_scale: Optional[tor
     """nn.BCEWithLogitsLoss()(exp(logit_scale) * z[:, :C], targets) (logit_scale None: scale 1) -> (loss fp32 [1], dz bf16
     [B, ldd] | None, dscale fp32 [1] | None, prob fp32 [B, C] | None = sigmoid of the scaled logits).  targets uint8 [B, C]."""
     _need(z, F32, "bce_logits.z"); _need(targets, torch.uint8, "bce_logits.targets")
+    return _bce("vipant_bce_logits", z, targets, logit_scale, C, row0, nrows, grad_scale, want_grad, ldd, want_prob)
+
+
+def bce_logits_soft(z: torch.Tensor, targets: torch.Tensor, logit_scale: Optional[torch.Tensor], *, C: Optional[int] = None,
+                    row0: int = 0, nrows: Optional[int] = None, grad_scale: float = 1.0, want_grad: bool = True,
+                    ldd: Optional[int] = None, want_prob: bool = False):
+    """bce_logits against soft targets fp32 [B, C] (mixup's lam y + (1 - lam) y'; not clamped to [0, 1]).  Targets that are
+    exactly 0 or 1 give bce_logits' bits."""
+    _need(z, F32, "bce_logits_soft.z"); _need(targets, F32, "bce_logits_soft.targets")
+    return _bce("vipant_bce_logits_soft", z, targets, logit_scale, C, row0, nrows, grad_scale, want_grad, ldd, want_prob)
+
+
+def _bce(entry, z, targets, logit_scale, C, row0, nrows, grad_scale, want_grad, ldd, want_prob):
     B = z.shape[0]
     C = z.shape[1] if C is None else int(C)
     assert targets.shape[0] == B and targets.shape[1] >= C, (z.shape, targets.shape)
@@ -1503,7 +1516,7 @@ def bce_logits(z: torch.Tensor, targets: torch.Tensor, logit_scale: Optional[tor
     dscale = torch.empty((1,), dtype=F32, device=dev) if (want_grad and ls is not None) else None
     prob = torch.empty((B, C), dtype=F32, device=dev) if want_prob else None
     ws = scratch("classify", query("vipant_bce_logits_workspace_bytes", nrows), dev)
-    call("vipant_bce_logits", z.data_ptr(), z.stride(0), targets.data_ptr(), targets.stride(0), _ptr(ls), loss.data_ptr(), _ptr(dz),
+    call(entry, z.data_ptr(), z.stride(0), targets.data_ptr(), targets.stride(0), _ptr(ls), loss.data_ptr(), _ptr(dz),
          ldd, _ptr(dscale), _ptr(prob), C, int(row0), nrows, float(grad_scale), B, C, ws.data_ptr(), ws.numel(), _stream())
     return loss, dz, dscale, prob
 
@@ -1537,11 +1550,11 @@ def padded_classifier(w: torch.Tensor, bias: Optional[torch.Tensor], Cp: int):
 
 class ClassifierMeta:
     """What ClassifierFn needs besides its differentiable inputs: the loss ("ce": int64 labels [B]; "bce": uint8 multi-hot
-    targets [B, C]), the class count, 1 / world for a replica's share of the gradient, and what the eval path wants back.
+    targets [B, C]; "bce_soft": fp32 soft targets [B, C]), the class count, 1 / world for a replica's share of the gradient, and what the eval path wants back.
     `pred` / `prob` receive the arg-max columns / sigmoid scores of the last forward."""
 
     def __init__(self, kind: str, nclass: int, grad_scale: float = 1.0, want_pred: bool = False, want_prob: bool = False):
-        assert kind in ("ce", "bce"), kind
+        assert kind in ("ce", "bce", "bce_soft"), kind
         self.kind, self.nclass, self.grad_scale = kind, int(nclass), float(grad_scale)
         self.want_pred, self.want_prob = bool(want_pred), bool(want_prob)
         self.pred = self.prob = None
@@ -1582,8 +1595,8 @@ class ClassifierFn(torch.autograd.Function):
                                              want_pred=meta.want_pred)
             meta.pred = pred
         else:
-            loss, dz, dls, prob = bce_logits(z, target, logit_scale, C=C, grad_scale=meta.grad_scale, want_grad=want,
-                                             want_prob=meta.want_prob)
+            bce = bce_logits_soft if meta.kind == "bce_soft" else bce_logits
+            loss, dz, dls, prob = bce(z, target, logit_scale, C=C, grad_scale=meta.grad_scale, want_grad=want, want_prob=meta.want_prob)
             meta.prob = prob
         if want:
             ctx.saved, ctx.dz, ctx.dls, ctx.wt, ctx.params = saved, dz, dls, wt, params
