@@ -189,7 +189,7 @@ __device__ __forceinline__ void load_codes(const GemmNT& p, int m0, int n0, int 
 }
 
 // `pre`: the codes of round 0, requested by the caller during the tile's last K-tile (QuickGELU' launch on the DEEP schedule: the
-// HBM round trip of the first round's codes is then off the epilogue's critical path), or NULL
+// HBM round trip of the first round's codes is then off the epilogue's critical path), or NULL: requested here with the other rounds'
 // EMIT: 0 = the bf16 result only; 1 = also its e4m3 form (p.cq, p.cqs); 2 = the e4m3 form ALONE (QuickGELU epilogue of a tower that
 // keeps neither g nor the derivative codes: their arithmetic is not compiled in); 3 = the e4m3 form and the derivative codes, no bf16
 // result (round 6: the e4m3 form is all the backward reads of g -- the weight-gradient contraction takes it as it is)
@@ -216,7 +216,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmNT& p, f32x4 (&acc)[8][4],
                 for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj) {
-                        const f32x4 u = acc[2 * r + ii][2 * jp + jj] + bv[2 * jp + jj];
+                        const f32x4 u = acc[2 * r + ii][2 * jp + jj] + (DGELU ? f32x4{0.f, 0.f, 0.f, 0.f} : bv[2 * jp + jj]);
                         b = fmaxf(fmaxf(b, fmaxf(fabsf(u[0]), fabsf(u[1]))), fmaxf(fabsf(u[2]), fabsf(u[3])));
                     }
                 // (DPP + readlane reduction: the result is a scalar, and so is everything derived from it)
@@ -244,9 +244,14 @@ __device__ __forceinline__ void pp_epilogue(const GemmNT& p, f32x4 (&acc)[8][4],
     constexpr bool GELU_OUT = EPI == VIPANT_EPI_QUICKGELU || EPI == VIPANT_EPI_QUICKGELU_D8;
     constexpr bool GELU_IN = EPI == VIPANT_EPI_DQUICKGELU || EPI == VIPANT_EPI_DQUICKGELU_D8;
     constexpr bool D8 = EPI == VIPANT_EPI_QUICKGELU_D8 || EPI == VIPANT_EPI_DQUICKGELU_D8;
-    // QuickGELU' inputs of the next round (bf16 pre-activations, or their 8-bit derivative codes), loaded one round ahead
-    bf16x8 un[4];
-    u32x2 cn[4];
+    // QuickGELU' inputs (bf16 pre-activations, or their 8-bit derivative codes) of ALL FOUR rounds, requested here, in front of the
+    // tile's first store, and awaited ONCE (`await_aux`, behind round 0's staging barrier).  The loads and the result stores sit behind
+    // bounds checks, and hipcc counts only what is issued on every path: with one round of look-ahead (the earlier form) each of the
+    // twelve stores of rounds 1-3 got an `s_waitcnt vmcnt(0)` of its own in front of it -- the codes just requested, the previous
+    // store's acknowledgement and, on thread 0's wave, the ticket atomic, twelve serial round trips per tile.  Now the rounds only
+    // store, as the BF16 epilogue's do (isa_guard.check_gemm_nt_epilogue holds the compiled code to that).
+    u32x4 un[4][4];
+    u32x2 cn[4][4];
     auto load_aux = [&](int r) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -254,17 +259,27 @@ __device__ __forceinline__ void pp_epilogue(const GemmNT& p, f32x4 (&acc)[8][4],
             const int R = idx >> 5, ch = idx & 31;
             const int m = m0 + grp * 128 + (r * 2 + (R >> 4)) * 16 + (R & 15), n = n0 + ch * 8;
             const bool ok = m < p.M && n < p.N;
-            if (D8) cn[t] = ok ? *(const u32x2*)((const uint8_t*)p.aux + (int64_t)m * p.ldc + n) : u32x2{0u, 0u};
-            else un[t] = ok ? *(const bf16x8*)((const bf16_t*)p.aux + (int64_t)m * p.ldc + n) : bf16x8{};
+            if (D8) cn[r][t] = ok ? *(const u32x2*)((const uint8_t*)p.aux + (int64_t)m * p.ldc + n) : u32x2{0u, 0u};
+            else un[r][t] = ok ? *(const u32x4*)((const bf16_t*)p.aux + (int64_t)m * p.ldc + n) : u32x4{0u, 0u, 0u, 0u};
+        }
+    };
+    // a use of every input register outside the bounds checks: the wait for the loads lands HERE, once, and not in front of each store
+    auto await_aux = [&]() {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (D8) asm volatile("" : "+v"(cn[r][0]), "+v"(cn[r][1]), "+v"(cn[r][2]), "+v"(cn[r][3]));
+            else asm volatile("" : "+v"(un[r][0]), "+v"(un[r][1]), "+v"(un[r][2]), "+v"(un[r][3]));
         }
     };
     if (GELU_IN) {
         if (pre != nullptr) {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) cn[t] = (*pre)[t];
+            for (int t = 0; t < 4; ++t) cn[0][t] = (*pre)[t];
         } else {
             load_aux(0);
         }
+#pragma unroll
+        for (int r = 1; r < 4; ++r) load_aux(r);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -275,17 +290,11 @@ __device__ __forceinline__ void pp_epilogue(const GemmNT& p, f32x4 (&acc)[8][4],
             for (int j = 0; j < 4; ++j) {
                 const int colbyte = wl * 128 + j * 32 + fq * 8;
                 *(bf16x4*)((ii ? stg_hi : stg) + (ii * 16 + frow) * 512 + (((colbyte >> 4) ^ frow) << 4) + (colbyte & 8)) =
-                    f32x4_to_bf16x4(acc[i][j] + bv[j]);
+                    f32x4_to_bf16x4(acc[i][j] + (GELU_IN ? f32x4{0.f, 0.f, 0.f, 0.f} : bv[j]));     // (QuickGELU' reads no bias; the caller leaves bv[] unset)
             }
         }
         sync();
-        bf16x8 u8[4];
-        u32x2 c8[4];
-        if (GELU_IN) {      // this round's inputs arrived during the previous round
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { u8[t] = un[t]; c8[t] = cn[t]; }
-            if (r + 1 < 4) load_aux(r + 1);
-        }
+        if (GELU_IN && r == 0) await_aux();
         if (EPI == VIPANT_EPI_QUICKGELU_D8 && (p.N & 15) == 0 && (p.ldc & 15) == 0) {
             // a thread takes 16 consecutive columns, so that the code leaves as one 16-B store per thread (the store path
             // is bound by instructions as much as by bytes: 6 instead of 8 store instructions per thread and round)
@@ -372,9 +381,9 @@ __device__ __forceinline__ void pp_epilogue(const GemmNT& p, f32x4 (&acc)[8][4],
                     for (int e = 0; e < 8; ++e) {
                         float dg;
                         if (D8) {
-                            dg = gelu_decode((c8[t][e >> 2] >> ((e & 3) * 8)) & 255u);
+                            dg = gelu_decode((cn[r][t][e >> 2] >> ((e & 3) * 8)) & 255u);
                         } else {
-                            const float u = (float)u8[t][e];
+                            const float u = (float)__builtin_bit_cast(bf16x8, un[r][t])[e];
                             const float sg = quickgelu_gate(u);
                             dg = sg * (1.0f + 1.702f * u * (1.0f - sg));
                         }
@@ -731,6 +740,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(GemmNT p) {
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // QuickGELU' reads no bias, and its kernels do not materialise one: a zero fill of bv[] in the last K-tile was ordered behind the
+        // round-0 code loads by a full wait (the allocator gave both the same registers) -- the LDS-DMA stream drained once per tile
+        constexpr bool HAS_BIAS = EPI != VIPANT_EPI_DQUICKGELU && EPI != VIPANT_EPI_DQUICKGELU_D8;
         f32x4 bv[4];
         constexpr bool PRE_CODES = DEEP && EPI == VIPANT_EPI_DQUICKGELU_D8;
         u32x2 cn_pre[4];
@@ -738,10 +750,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(GemmNT p) {
             const int stage = gk & 1;
             const int slot1 = slot == 2 ? 0 : slot + 1, slot2 = slot1 == 2 ? 0 : slot1 + 1;
             if (k == nk - 1) {                   // the tile's bias: fetched and awaited before this K-tile's DMA is queued
-                load_bias<EPI>(p, cur.n0, wl, fq, bv);
+                if constexpr (HAS_BIAS) load_bias<EPI>(p, cur.n0, wl, fq, bv);
                 if (ES == 1) load_b_scales(nxt, sbv_n);                       // the next tile's weight scales ride the same round trip
+                if constexpr (HAS_BIAS) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(bv[j]));
+                    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(bv[j]));
+                }
                 if (ES == 1) asm volatile("" : "+v"(sbv_n));
                 if (dyn) {
                     // the ticket drawn one epilogue ago has returned with the loads above: publish it for the next tile's round trip
@@ -831,9 +845,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(GemmNT p) {
         // counted wait -- which lets the K-tile's eight pieces stay in flight -- had to see its acknowledgement first (+0.5 us per tile
         // on the launches with a bias); here the tile's own stores queue up behind it and nobody waits for it in particular
         // (What the draw still costs, round 5, bits switched off one by one in a test build: nothing measurable on the launches whose
-        // epilogue only stores; 10-25 us per launch on QuickGELU', whose epilogue waits for its code loads every round -- vmcnt retires
-        // in order, so thread 0's wave sees those loads only when the atomic, a ~2 us round trip, is back too, wherever in the
-        // epilogue it is issued, and the other waves meet it at the round's barrier.)
+        // epilogue only stores; 10-25 us per launch on QuickGELU', whose epilogue waits for its input loads -- vmcnt retires in order,
+        // so thread 0's wave sees those loads only when the atomic, a ~2 us round trip, is back too, and the other waves meet it at
+        // the round's barrier.  That epilogue now waits once per tile, not every round; the draw still sits in front of that wait
+        // (ticket 772 us against 743 us static, alone on the chip).  Issued behind round 0's stores it is no longer guaranteed-older
+        // than anything, and the wait for its value in the next tile's last K-tile turns from a counted one into a full one inside the
+        // K-loop; issued directly behind the input wait it costs the step's kernel five spilled registers.  Both built, neither kept.)
         if (dyn && tid == 0) {
             tickets::post_g(mbox + 4 * tk_par, tk_post);
             if (!tk_dry && !tk_half) tk_pend = tickets::take_g(tkq, (uint32_t)tk_n);      // not awaited here

@@ -1,5 +1,6 @@
 """ISA guards: kernels whose correctness rests on what the compiler put between two instructions it cannot relate -- inline-asm loads
-awaited by hand-counted `s_waitcnt vmcnt(n)` (csrc/attention.hip: mha_bwd1s_kernel; csrc/gemm_nt.hip: the ticket walk's mailbox word).
+awaited by hand-counted `s_waitcnt vmcnt(n)` (csrc/attention.hip: mha_bwd1s_kernel; csrc/gemm_nt.hip: the ticket walk's mailbox word) --
+or whose speed rests on a wait the compiler must NOT put there (csrc/gemm_nt.hip: no full wait between a tile epilogue's stores).
 The checks read the device assembly `-save-temps` leaves beside the object of the SAME compile that produced the shipped code
 (vipant_amd/lib/obj/<name>-hip-amdgcn-amd-amdhsa-gfx950.s) and raise AssertionError.  `vipant_amd.build` runs them after compiling and
 fails the build if one does not hold (a toolchain that moves or spills one of these registers must not produce a library);
@@ -86,4 +87,60 @@ def check_gemm_nt(path: str) -> None:
         assert not bad, (name, reg, bad)
 
 
-CHECKS = {"attention.hip": check_attention, "gemm_nt.hip": check_gemm_nt}
+_PP_KERNEL = re.compile(r"^(_ZN\S*gemm_nt_pp_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])E\S*):[^\n]*\n(.*?)\n\s*s_endpgm", flags=re.S | re.M)
+_FULL_WAIT = re.compile(r"^\s*s_waitcnt\b[^;\n]*\bvmcnt\(0\)")
+_DGELU = (4, 7)             # VIPANT_EPI_DQUICKGELU, VIPANT_EPI_DQUICKGELU_D8
+
+
+def pp_epilogue_waits(path: str):
+    """{(epilogue, schedule, element size, emit, ticket): (full waits in front of the first result store, full waits between the first
+    and the last result store, result stores)} for every gemm_nt_pp_kernel instantiation of the kept assembly, in program text.  A
+    result store is a 16-byte store (8 bf16 results); the kernels that leave the e4m3 form alone have none, their 8-byte stores count."""
+    assert os.path.exists(path), path
+    out = {}
+    for name, epi, var, es, emit, dyn, code in _PP_KERNEL.findall(open(path).read()):
+        lines = [l.split(";")[0] for l in code.split("\n")]
+        stores = [i for i, l in enumerate(lines) if re.match(r"\s*(global|buffer)_store_dwordx4\b", l)]
+        if not stores:
+            stores = [i for i, l in enumerate(lines) if re.match(r"\s*(global|buffer)_store_dwordx2\b", l)]
+        assert len(stores) >= 4, (name, stores)
+        full = [i for i, l in enumerate(lines) if _FULL_WAIT.match(l)]
+        out[(int(epi), int(var), int(es), int(emit), int(dyn))] = (sum(i < stores[0] for i in full), sum(stores[0] < i < stores[-1] for i in full),
+                                                                   len(stores))
+    return out
+
+
+def check_gemm_nt_epilogue(path: str) -> None:
+    """The tile epilogue of the ping-pong kernels stores 16 x 16 bytes per thread behind bounds checks.  hipcc counts only memory operations
+    issued on every path, so a load whose result is first used behind such a check, with a store in between, is awaited with
+    `s_waitcnt vmcnt(0)`: every store's acknowledgement, and the LDS-DMA stream of the next tile with it.  The QuickGELU' epilogues
+    (which read a code or a pre-activation per result) therefore request all their inputs in front of the first store and await them
+    once, outside the checks.  For EVERY instantiation, QuickGELU' or not:
+      * between the first and the last result store of the program text there is no full wait (the epilogue's blocks are laid out in
+        source order between the K-loop and the loop's back edge, so the span is the epilogue's four rounds and nothing else);
+    and for the QuickGELU' instantiations, against the BF16 instantiation of the same schedule, element size and walk:
+      * in front of the first store there are no more full waits than the BF16 kernel has, plus the one that awaits the inputs; the bf16
+        kernels have no bias round trip (QuickGELU' reads no bias, and no zero fill may stand in for one), which takes one off again.
+    No wait of the epilogue is hand-counted: there is no register to guard."""
+    table = pp_epilogue_waits(path)
+    assert len(table) >= 40, len(table)
+    dgelu = [k for k in table if k[0] in _DGELU]
+    assert len(dgelu) >= 14 and {k[0] for k in table} >= {0, 6}, sorted(table)
+    for key, (before, inside, n) in sorted(table.items()):
+        assert inside == 0, (key, "full waits between the result stores", inside)
+    for key in dgelu:
+        epi, var, es, emit, dyn = key
+        deep = var in (10, 12)
+        twins = [k for k in table if k[0] == 0 and k[2] == es and k[3] == 0 and k[4] == dyn and (k[1] in (10, 12)) == deep]
+        assert twins, key
+        twin = (0, var, es, 0, dyn) if (0, var, es, 0, dyn) in twins else min(twins)
+        allowed = table[twin][0] + 1 - (1 if es == 2 else 0)
+        assert table[key][0] <= allowed, (key, "full waits in front of the first result store", table[key][0], "BF16 twin", twin, table[twin][0])
+
+
+def _check_gemm_nt_all(path: str) -> None:
+    check_gemm_nt(path)
+    check_gemm_nt_epilogue(path)
+
+
+CHECKS = {"attention.hip": check_attention, "gemm_nt.hip": _check_gemm_nt_all}
