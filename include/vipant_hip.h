@@ -388,6 +388,55 @@ int32_t vipant_fbank_mix(const float* wave, int64_t wave_stride, const int64_t* 
                          const int32_t* mix_index, const float* mix_lambda, int64_t b, int64_t T, int64_t F,
                          int32_t window_size, int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean,
                          float norm_std, void* workspace, size_t workspace_bytes, void* stream);
+/* vipant_fbank on a VIEW of every clip: the reference's waveform transforms and its crop rule (cvap/data/audio/transform.py:75-202
+ * and :24-28) inside the launch.  A clip passes, in this order, through
+ *   flip     s1[i] = s0[n0-1-i] when its flip draw is >= 0.5;
+ *   scale    by the factor c of its draw: n2 = int(n1 c) (product in double, at most 2^24 - 1), base = float(j) / float(c) (IEEE
+ *            fp32 division), r1 = trunc(base), r2 = min(r1 + 1, n1 - 1), r = base - r1, s2[j] = (1 - r) s1[r1] + r s1[r2]
+ *            (one product and one fused multiply-add);
+ *   pad      to pad_len when shorter: left = min(floor(u (pad_len - n2)), pad_len - n2 - 1); filled with s2[0] / s2[n2-1], or
+ *            with padding_value when has_padding_value;
+ *   crop     to crop_len when longer, by the CROP RULE: left = min(floor(u (n - len)), n - len - 1); with unbiased standard
+ *            deviations, when the window's is below half the whole signal's the head [0, len) is taken instead, and when the
+ *            head's is lower still, the tail;
+ *   noise    when its snr draw is >= 0: sigma = sqrt(10^((10 log10(mean(s4^2)) - snr) / 10) + 1e-7), s5[k] = s4[k] + sigma z(k), z a
+ *            counter-based normal: Philox4x32-10, key (seed low word, seed high word ^ clip), counter (k >> 2, 0, 0, 0), output word
+ *            k & 3 for sample k; Box-Muller over the word pairs (0, 1) and (2, 3) with u = ((word >> 9) + 0.5) 2^-23:
+ *            sqrt(-2 log u) cospi(2 v) for the even member of a pair, sinpi for the odd one;
+ *   the pipeline's crop to final_len by the same rule (drawn when `train`; otherwise centred, left = 0.5 (n - len) rounded half
+ *            to even) -- always;
+ *   minus the mean of the result when zero_mean.
+ * `stages` (VIPANT_VIEW_*) enables flip / scale / pad / crop / noise for the whole batch.  draws fp64 [b, 6] on the device =
+ * (flip, scale, pad u, crop u, snr or < 0 for "no noise", final u) per clip.  The host cannot see them: a u outside [0, 1) is
+ * clamped into it and a scale that is not positive leaves the clip unscaled.  None of the intermediate signals is stored:
+ * `workspace` (vipant_fbank_view_workspace_bytes(b)) holds one 64-byte plan per clip, resolved by one reduction launch (fixed
+ * order, statistics in double, no float atomics), and the frame loader maps each sample back to its one or two source samples.
+ * A plan is sixteen 32-bit words: int32 n0, n2 (after scale), n3 (after pad), n4 (after crop), n_out, flags (1 flipped, 2 scaled,
+ * 4 noisy), pad_left, crop_left, final_left (the lefts of what the rule TOOK); fp32 c, fill_l, fill_r, sigma, mean; the Philox key.
+ * A clip no stage touches (and no longer than final_len) gets the bits of vipant_fbank(..., zero_mean).  From the waveform on the
+ * pipeline is vipant_fbank's.  vipant_wave_view writes the final waveform itself (same plan, same sample function, same bits):
+ * wave_out fp32 [b, out_stride], zero beyond a clip's length, and the lengths (at most out_stride) as nsamples_out int64 [b].
+ * A NULL argument (masks excepted), b = 0 or a bad shape is refused and nothing is written. */
+#define VIPANT_VIEW_FLIP 1
+#define VIPANT_VIEW_SCALE 2
+#define VIPANT_VIEW_PAD 4
+#define VIPANT_VIEW_CROP 8
+#define VIPANT_VIEW_NOISE 16
+typedef struct vipant_view_params {
+    int64_t pad_len, crop_len, final_len;
+    uint64_t seed;
+    float padding_value;
+    int32_t has_padding_value, train, zero_mean, stages, reserved;
+} vipant_view_params;
+size_t vipant_fbank_view_workspace_bytes(int64_t b);
+int32_t vipant_fbank_view(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, const float* window,
+                          const float* banks, const int32_t* bank_start, const int32_t* bank_len, const int32_t* masks,
+                          int64_t b, int64_t T, int64_t F, int32_t window_size, int32_t window_shift, int32_t nfft,
+                          float preemphasis, float norm_mean, float norm_std, vipant_view_params view, const double* draws,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int32_t vipant_wave_view(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* wave_out, int64_t out_stride,
+                         int64_t* nsamples_out, int64_t b, vipant_view_params view, const double* draws, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---- LARS (cvap/module/lars.py:43-72), one fused pass per tensor list ---------------------------------
  * For tensor i (n[i] elements): dp = g + wd*p (adapt[i]); q = eta*|p|/|dp| (adapt[i], both norms > 0);

@@ -36,6 +36,15 @@ class Fp8Plan(C.Structure):
                 ("keep2_q", _p), ("keep2_scale", _p)]
 
 
+VIEW_FLIP, VIEW_SCALE, VIEW_PAD, VIEW_CROP, VIEW_NOISE = 1, 2, 4, 8, 16     # VIPANT_VIEW_*
+
+
+class ViewParams(C.Structure):
+    """struct vipant_view_params (include/vipant_hip.h): the static parameters of vipant_fbank_view / vipant_wave_view, by value."""
+    _fields_ = [("pad_len", _i64), ("crop_len", _i64), ("final_len", _i64), ("seed", C.c_uint64), ("padding_value", _f32),
+                ("has_padding_value", _i32), ("train", _i32), ("zero_mean", _i32), ("stages", _i32), ("reserved", _i32)]
+
+
 # name -> (restype, argtypes); mirrors include/vipant_hip.h one to one
 PROTOTYPES = {
     "vipant_last_error": (C.c_char_p, []),
@@ -100,6 +109,9 @@ PROTOTYPES = {
     "vipant_fbank": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _f32, _f32, _p, _sz, _p]),
     "vipant_fbank_mix_workspace_bytes": (_sz, [_i64]),
     "vipant_fbank_mix": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _p, _sz, _p]),
+    "vipant_fbank_view_workspace_bytes": (_sz, [_i64]),
+    "vipant_fbank_view": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, ViewParams, _p, _p, _sz, _p]),
+    "vipant_wave_view": (_i32, [_p, _i64, _p, _p, _i64, _p, _i64, ViewParams, _p, _p, _sz, _p]),
     # fused operator set (vipant_amd/csrc/block.hip)
     "vipant_block_workspace_bytes": (_sz, [_i64, _i64]),
     "vipant_ln_qkv_fwd": (_i32, [_p] * 11 + [_i64, _i64, _p, _i32, _p]),

@@ -20,7 +20,8 @@ struct FbankArgs {
     const float* wave; int64_t wave_stride; const int64_t* nsamples; float* out;
     const float* window; const float* banks; const int32_t* bank_start; const int32_t* bank_len; const int32_t* masks;
     const float* clip_mean;
-    const int32_t* mix_index; const float* mix_lambda; const float* mix_mean;      // vipant_fbank_mix only
+    union { const int32_t* mix_index; const struct ViewPlan* plan; };               // vipant_fbank_mix / vipant_fbank_view only
+    const float* mix_lambda; const float* mix_mean;                                // vipant_fbank_mix only
     int T, F, size, shift;
     float preemph, norm_mean, norm_std;
 };
@@ -88,6 +89,218 @@ __global__ __launch_bounds__(MIX_MEAN_THREADS) void mix_mean_kernel(const float*
     if (threadIdx.x == 0) mix_mean[clip] = n > 0 ? red[0] / (float)n : 0.f;
 }
 
+// ---- waveform views: the reference's waveform transforms and its crop rule (cvap/data/audio/transform.py:75-202, :24-28) ----------
+// A clip passes through flip -> scale -> pad -> crop -> noise -> the pipeline's crop -> zero-mean.  None of the intermediate signals
+// is stored: view_plan_kernel resolves every data-dependent decision of a clip (the crop rule compares standard deviations, the noise
+// level follows the signal power) into a 64-byte plan, and view_sample() maps an output index back through the stages to one or two
+// source samples.  Everything that needs the signal -- the plan's own reductions, the log-mel frame loader, wave_view_kernel --
+// calls view_sample, so all of them see the same bits.
+enum : int32_t { VIEW_FLIP = VIPANT_VIEW_FLIP, VIEW_SCALE = VIPANT_VIEW_SCALE, VIEW_PAD = VIPANT_VIEW_PAD, VIEW_CROP = VIPANT_VIEW_CROP,
+                 VIEW_NOISE = VIPANT_VIEW_NOISE };
+enum : int32_t { PLAN_FLIP = 1, PLAN_SCALED = 2, PLAN_NOISY = 4 };
+
+struct ViewPlan {
+    int32_t n0, n2, n3, n4, n_out;          // lengths: source (= after flip), after scale, after pad, after crop (what the noise sees), final
+    int32_t flags;                          // PLAN_*
+    int32_t pad_left, crop_left, final_left;
+    float c, fill_l, fill_r, sigma, mean;   // scale factor, pad values, noise level, mean of the final window (0 without zero_mean)
+    uint32_t key0, key1;                    // Philox key of the clip
+};
+static_assert(sizeof(ViewPlan) == 64, "plan layout");
+
+// z(seed, clip, k): Philox4x32-10 with key (seed_lo, seed_hi ^ clip) and counter (k >> 2, 0, 0, 0); word k & 3 serves sample k, and
+// Box-Muller runs over the word pairs (0, 1) and (2, 3) -- a function of k alone, because a sample is loaded by up to three
+// overlapping frames and by the reductions and must have the same value every time.
+__device__ __forceinline__ float view_normal(uint32_t k0, uint32_t k1, uint32_t k) {
+    uint32_t c0 = k >> 2, c1 = 0u, c2 = 0u, c3 = 0u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0, h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    const bool second = (k & 2u) != 0u;
+    const uint32_t wu = second ? c2 : c0, wv = second ? c3 : c1;
+    const float u = __fmul_rn((float)(wu >> 9) + 0.5f, 0x1p-23f), v = __fmul_rn((float)(wv >> 9) + 0.5f, 0x1p-23f);   // exact, in (0, 1)
+    const float rad = sqrtf(__fmul_rn(-2.0f, logf(u)));
+    return __fmul_rn(rad, (k & 1u) ? sinpif(__fmul_rn(2.0f, v)) : cospif(__fmul_rn(2.0f, v)));
+}
+
+// sample i of the scaled (and flipped) clip, 0 <= i < n2.  The blend is pinned (one product, one fused multiply-add) so that every
+// kernel that inlines this rounds alike.
+__device__ __forceinline__ float view_scaled(const ViewPlan& p, const float* __restrict__ w, int i) {
+    const int last = p.n0 - 1;
+    if (p.flags & PLAN_SCALED) {
+        const float base = (float)i / p.c;                                    // IEEE fp32 division, as torch's arange().div_()
+        int r1 = (int)base;
+        r1 = r1 < last ? r1 : last;
+        const int r2 = r1 + 1 < last ? r1 + 1 : last;
+        const float r = base - (float)r1;
+        const float a = w[(p.flags & PLAN_FLIP) ? last - r1 : r1], b = w[(p.flags & PLAN_FLIP) ? last - r2 : r2];
+        return __fmaf_rn(r, b, __fmul_rn(1.0f - r, a));
+    }
+    i = i < last ? i : last;
+    return w[(p.flags & PLAN_FLIP) ? last - i : i];
+}
+
+// sample j of the clip's final window, 0 <= j < n_out.  A plan whose later stages are not resolved yet (crop_left = final_left = 0,
+// no noise, mean = 0) yields the signal in front of those stages: this is how view_plan_kernel's reductions use it.
+__device__ __forceinline__ float view_sample(const ViewPlan& p, const float* __restrict__ w, int j) {
+    const int k = j + p.final_left;                                           // index into the cropped signal: the noise counter
+    const int i = k + p.crop_left - p.pad_left;                               // index into the scaled signal; outside it: padding
+    float x = i < 0 ? p.fill_l : (i >= p.n2 ? p.fill_r : view_scaled(p, w, i));
+    if (p.flags & PLAN_NOISY) x = __fmaf_rn(p.sigma, view_normal(p.key0, p.key1, (uint32_t)k), x);
+    return x - p.mean;
+}
+
+constexpr int VIEW_PLAN_THREADS = 1024;
+
+// sum of eight doubles per thread over the workgroup, in a fixed order: butterfly within a wave, the waves' sums through LDS, every
+// thread then adds them in wave order (so all threads hold the same totals)
+__device__ __forceinline__ void view_reduce8(double (&v)[8], double (*red)[8]) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        double x = v[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+        if (lane == 0) red[wv][q] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        double x = 0.0;
+        for (int i = 0; i < VIEW_PLAN_THREADS / 64; ++i) x += red[i][q];
+        v[q] = x;
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ double view_var(double s, double q, int n) {      // unbiased, as torch.std
+    const double v = (q - s * s / (double)n) / (double)(n - 1);
+    return v > 0.0 ? v : 0.0;
+}
+
+__device__ __forceinline__ double view_unit(double u) { return u >= 0.0 ? (u < 1.0 ? u : 0x1.fffffffffffffp-1) : 0.0; }    // into [0, 1); NaN -> 0
+
+// RandomCrop.random_crop (transform.py:122-141) of the signal view_sample(p, w, 0 .. n) to length len (< n): the drawn (or centred)
+// window, unless its standard deviation is below half the clip's -- then the head, or the tail if the head is quieter still.
+// Sums and sums of squares over the four windows (whole, drawn, head, tail) come from ONE pass, in double: these are variances of
+// 10^5 samples that are then compared with each other.
+__device__ __forceinline__ int view_crop_rule(const ViewPlan& p, const float* __restrict__ w, int n, int len, double u, bool center,
+                                              double (*red)[8]) {
+    const int d = n - len;
+    int left;
+    if (center) left = (d >> 1) + ((d & 1) ? ((d >> 1) & 1) : 0);            // int(round(0.5 * d)): half to even
+    else {
+        const double f = floor(view_unit(u) * (double)d);
+        left = f < (double)(d - 1) ? (int)f : d - 1;                          // np.random.randint(0, d) never returns d
+    }
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += VIEW_PLAN_THREADS) {
+        const double x = (double)view_sample(p, w, i), xx = x * x;
+        a[0] += x; a[1] += xx;
+        if (i >= left && i < left + len) { a[2] += x; a[3] += xx; }
+        if (i < len) { a[4] += x; a[5] += xx; }
+        if (i >= d) { a[6] += x; a[7] += xx; }
+    }
+    view_reduce8(a, red);
+    const double old_var = 0.25 * view_var(a[0], a[1], n), new_var = view_var(a[2], a[3], len);
+    if (!(new_var < old_var)) return left;
+    const double head_var = view_var(a[4], a[5], len);
+    return new_var > head_var ? d : 0;
+}
+
+struct ViewParams { int32_t pad_len, crop_len, final_len, stages, train, zero_mean, has_padding_value; float padding_value; uint32_t seed_lo, seed_hi; };
+
+__global__ __launch_bounds__(VIEW_PLAN_THREADS) void view_plan_kernel(const float* __restrict__ wave, int64_t stride,
+                                                                      const int64_t* __restrict__ nsamples,
+                                                                      const double* __restrict__ draws, ViewParams vp,
+                                                                      ViewPlan* __restrict__ plans) {
+    __shared__ double red[VIEW_PLAN_THREADS / 64][8];
+    __shared__ float redf[256];
+    const int clip = blockIdx.x;
+    const float* w = wave + (int64_t)clip * stride;
+    int64_t n0 = nsamples[clip];
+    n0 = n0 < 0 ? 0 : (n0 < stride ? n0 : stride);
+    ViewPlan p;
+    p.n0 = p.n2 = p.n3 = p.n4 = p.n_out = (int)n0;
+    p.flags = 0;
+    p.pad_left = p.crop_left = p.final_left = 0;
+    p.c = 1.f; p.fill_l = p.fill_r = p.sigma = p.mean = 0.f;
+    p.key0 = vp.seed_lo; p.key1 = vp.seed_hi ^ (uint32_t)clip;
+    if (n0 == 0) {                                                // uniform over the workgroup: an empty clip stays empty
+        if (threadIdx.x == 0) plans[clip] = p;
+        return;
+    }
+    const double* dr = draws + (int64_t)clip * 6;
+    const double flip = dr[0], scale = dr[1], pad_u = dr[2], crop_u = dr[3], snr = dr[4], final_u = dr[5];
+    if ((vp.stages & VIEW_FLIP) && flip >= 0.5) p.flags |= PLAN_FLIP;
+    if ((vp.stages & VIEW_SCALE) && scale > 0.0 && scale != 1.0) {            // a factor that is not positive (or NaN) leaves the clip as it is
+        double m = floor((double)p.n0 * scale);                               // int(n * scaling), the product in double
+        m = m < 1.0 ? 1.0 : (m < 16777215.0 ? m : 16777215.0);                // fp32 indices are exact below 2^24
+        p.n2 = (int)m; p.c = (float)scale; p.flags |= PLAN_SCALED;
+    }
+    p.n3 = p.n2;
+    if ((vp.stages & VIEW_PAD) && p.n2 < vp.pad_len) {
+        const int d = vp.pad_len - p.n2;
+        const double f = floor(view_unit(pad_u) * (double)d);
+        p.pad_left = f < (double)(d - 1) ? (int)f : d - 1;                    // np.random.randint(0, d) never returns d
+        p.fill_l = vp.has_padding_value ? vp.padding_value : view_scaled(p, w, 0);
+        p.fill_r = vp.has_padding_value ? vp.padding_value : view_scaled(p, w, p.n2 - 1);
+        p.n3 = vp.pad_len;
+    }
+    p.n4 = p.n3;
+    if ((vp.stages & VIEW_CROP) && p.n3 > vp.crop_len) {
+        p.crop_left = view_crop_rule(p, w, p.n3, vp.crop_len, crop_u, false, red);
+        p.n4 = vp.crop_len;
+    }
+    if ((vp.stages & VIEW_NOISE) && snr >= 0.0) {                             // RandomNoise.random_noise (transform.py:186-199)
+        double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int i = threadIdx.x; i < p.n4; i += VIEW_PLAN_THREADS) {
+            const double x = (double)view_sample(p, w, i);
+            a[0] += x * x;
+        }
+        view_reduce8(a, red);
+        const double power = a[0] / (double)p.n4;
+        const float watts = (power > 0.0 ? (float)pow(10.0, (10.0 * log10(power) - snr) / 10.0) : 0.f) + 1e-7f;
+        p.sigma = (float)sqrt((double)watts);
+        p.flags |= PLAN_NOISY;
+    }
+    p.n_out = p.n4;
+    if (p.n4 > vp.final_len) {
+        p.final_left = view_crop_rule(p, w, p.n4, vp.final_len, final_u, !vp.train, red);
+        p.n_out = vp.final_len;
+    }
+    if (vp.zero_mean) {                                           // clip_mean_kernel's order (256 strided partial sums, LDS tree), so that a
+        float s = 0.f;                                            // clip with nothing to do gets vipant_fbank's mean to the bit
+        if (threadIdx.x < 256)
+            for (int i = threadIdx.x; i < p.n_out; i += 256) s += view_sample(p, w, i);
+        if (threadIdx.x < 256) redf[threadIdx.x] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) redf[threadIdx.x] += redf[threadIdx.x + o];
+            __syncthreads();
+        }
+        p.mean = redf[0] / (float)p.n_out;
+    }
+    if (threadIdx.x == 0) plans[clip] = p;
+}
+
+// the final waveform itself, for callers that want it (and for the tests): [b, out_stride], zero beyond a clip's n_out
+__global__ __launch_bounds__(256) void wave_view_kernel(const float* __restrict__ wave, int64_t stride, const ViewPlan* __restrict__ plans,
+                                                        float* __restrict__ out, int64_t out_stride, int64_t* __restrict__ nsamples_out,
+                                                        int64_t b) {
+    const int64_t total = b * out_stride, step = (int64_t)gridDim.x * 256;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += step) {
+        const int64_t clip = e / out_stride, j = e - clip * out_stride;
+        const ViewPlan p = plans[clip];
+        const int64_t n = p.n_out < out_stride ? p.n_out : out_stride;
+        out[e] = j < n ? view_sample(p, wave + clip * stride, (int)j) : 0.f;
+        if (j == 0) nsamples_out[clip] = n;
+    }
+}
+
 // LDS traffic of one wave is processed in program order, and a frame is private to its wave: between FFT passes it is
 // enough to stop the compiler from moving LDS accesses across the pass boundary.
 __device__ __forceinline__ void wave_lds_sync() {
@@ -100,8 +313,11 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 w) { return make_float2(
 constexpr int FPW = 4;            // frame PAIRS per wave: the workgroup's tables (twiddles, window, mel weights) serve 32 frames
 constexpr int MAXF = 256;         // mel bins
 
-// MIX: a clip with a partner forms its samples from two sources on the way into LDS (the mixed waveform is never stored)
-template <int NFFT, bool MIX>
+// MODE_MIX: a clip with a partner forms its samples from two sources on the way into LDS (the mixed waveform is never stored).
+// MODE_VIEW: the clip's length comes from its plan and the samples from view_sample (the transformed waveform is never stored).
+enum : int { MODE_PLAIN = 0, MODE_MIX = 1, MODE_VIEW = 2 };
+
+template <int NFFT, int MODE>
 __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_off[MAXF + 1], s_start[MAXF], s_len[MAXF];
@@ -139,7 +355,14 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     }
     __syncthreads();
 
-    const int64_t n = a.nsamples[clip];
+    ViewPlan plan;
+    int64_t n;
+    if constexpr (MODE == MODE_VIEW) {
+        plan = a.plan[clip];
+        n = plan.n_out;
+    } else {
+        n = a.nsamples[clip];
+    }
     const int nframes = n < a.size ? 0 : (int)(1 + (n - a.size) / a.shift);
     const float cmean = a.clip_mean != nullptr ? a.clip_mean[clip] : 0.f;
     const int32_t* mk = a.masks != nullptr ? a.masks + (int64_t)clip * 4 : nullptr;
@@ -148,7 +371,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     int partner = -1;
     int64_t np = 0;
     float lam = 1.f, oml = 0.f, pmean = 0.f, xmean = 0.f;
-    if constexpr (MIX) {
+    if constexpr (MODE == MODE_MIX) {
         partner = mix_partner(a.mix_index, clip, (int)gridDim.y);
         if (partner >= 0) {
             np = a.nsamples[partner] < a.wave_stride ? a.nsamples[partner] : a.wave_stride;
@@ -184,9 +407,16 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
         float* raw_b = raw + NFFT;
         float sa = 0.f, sb = 0.f;
         for (int j = lane; j < a.size; j += 64) {
-            float xa = live_a ? src[j] - cmean : 0.f;
-            float xb = live_b ? src[j + a.shift] - cmean : 0.f;
-            if constexpr (MIX) {
+            float xa, xb;
+            if constexpr (MODE == MODE_VIEW) {
+                const float* w = a.wave + (int64_t)clip * a.wave_stride;
+                xa = live_a ? view_sample(plan, w, ta * a.shift + j) : 0.f;
+                xb = live_b ? view_sample(plan, w, tb * a.shift + j) : 0.f;
+            } else {
+                xa = live_a ? src[j] - cmean : 0.f;
+                xb = live_b ? src[j + a.shift] - cmean : 0.f;
+            }
+            if constexpr (MODE == MODE_MIX) {
                 if (partner >= 0) {                               // the ORIGINAL partner clip, truncated / zero-padded to this clip
                     const int64_t ja = (int64_t)ta * a.shift + j, jb = ja + a.shift;
                     if (live_a) xa = (lam * xa + oml * (ja < np ? psrc[ja] - pmean : 0.f)) - xmean;
@@ -276,15 +506,15 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     }
 }
 
-template <int NFFT, bool MIX>
+template <int NFFT, int MODE>
 int32_t launch_fbank(const FbankArgs& a, int64_t b, hipStream_t s) {
     static DeviceOnce once;
     const size_t lds = ((size_t)4 * 2 * NFFT + NFFT / 2) * sizeof(float2) + (size_t)2 * NFFT * sizeof(float);
     if (first_on_device(once)) {
-        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)fbank_kernel<NFFT, MIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)fbank_kernel<NFFT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         done_on_device(once);
     }
-    hipLaunchKernelGGL((fbank_kernel<NFFT, MIX>), dim3((unsigned)((a.T + 8 * FPW - 1) / (8 * FPW)), (unsigned)b), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((fbank_kernel<NFFT, MODE>), dim3((unsigned)((a.T + 8 * FPW - 1) / (8 * FPW)), (unsigned)b), dim3(256), lds, s, a);
     VIPANT_LAUNCH_CHECK();
     return VIPANT_OK;
 }
@@ -316,9 +546,9 @@ extern "C" int32_t vipant_fbank(const float* wave, int64_t wave_stride, const in
     FbankArgs a{wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, cmean, nullptr, nullptr, nullptr,
                 (int)T, (int)F, window_size, window_shift, preemphasis, norm_mean, norm_std};
     switch (nfft) {
-        case 512: return launch_fbank<512, false>(a, b, s);
-        case 1024: return launch_fbank<1024, false>(a, b, s);
-        default: return launch_fbank<2048, false>(a, b, s);
+        case 512: return launch_fbank<512, MODE_PLAIN>(a, b, s);
+        case 1024: return launch_fbank<1024, MODE_PLAIN>(a, b, s);
+        default: return launch_fbank<2048, MODE_PLAIN>(a, b, s);
     }
 }
 
@@ -349,8 +579,75 @@ extern "C" int32_t vipant_fbank_mix(const float* wave, int64_t wave_stride, cons
     FbankArgs a{wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, cmean, mix_index, mix_lambda, xmean,
                 (int)T, (int)F, window_size, window_shift, preemphasis, norm_mean, norm_std};
     switch (nfft) {
-        case 512: return launch_fbank<512, true>(a, b, s);
-        case 1024: return launch_fbank<1024, true>(a, b, s);
-        default: return launch_fbank<2048, true>(a, b, s);
+        case 512: return launch_fbank<512, MODE_MIX>(a, b, s);
+        case 1024: return launch_fbank<1024, MODE_MIX>(a, b, s);
+        default: return launch_fbank<2048, MODE_MIX>(a, b, s);
     }
+}
+
+// one 64-byte plan per clip
+extern "C" size_t vipant_fbank_view_workspace_bytes(int64_t b) { return (size_t)((b * (int64_t)sizeof(ViewPlan) + 255) / 256 * 256); }
+
+namespace {
+
+// the checks the two view entry points share, and the plan launch; nothing is launched unless everything holds
+int32_t launch_view_plan(const char* who, const float* wave, int64_t wave_stride, const int64_t* nsamples, int64_t b,
+                         const vipant_view_params& vp, const double* draws, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    VIPANT_REQUIRE(b > 0 && b < 65536 && wave_stride > 0 && wave_stride < (int64_t)1 << 31, VIPANT_EBADSHAPE, "%s: bad batch b=%ld stride=%ld", who,
+                   (long)b, (long)wave_stride);
+    VIPANT_REQUIRE(wave != nullptr && nsamples != nullptr && draws != nullptr, VIPANT_EBADSHAPE, "%s: null argument", who);
+    const int64_t lim = (int64_t)1 << 30;
+    VIPANT_REQUIRE(vp.final_len >= 2 && vp.final_len < lim, VIPANT_EBADSHAPE, "%s: final length %ld outside [2, 2^30)", who, (long)vp.final_len);
+    VIPANT_REQUIRE(!(vp.stages & VIEW_PAD) || (vp.pad_len >= 1 && vp.pad_len < lim), VIPANT_EBADSHAPE, "%s: pad length %ld outside [1, 2^30)", who,
+                   (long)vp.pad_len);
+    VIPANT_REQUIRE(!(vp.stages & VIEW_CROP) || (vp.crop_len >= 2 && vp.crop_len < lim), VIPANT_EBADSHAPE, "%s: crop length %ld outside [2, 2^30)", who,
+                   (long)vp.crop_len);
+    VIPANT_REQUIRE((vp.stages & ~31) == 0, VIPANT_EBADSHAPE, "%s: unknown stage bits 0x%x", who, (unsigned)vp.stages);
+    VIPANT_REQUIRE(workspace != nullptr && workspace_bytes >= vipant_fbank_view_workspace_bytes(b), VIPANT_ENOWORKSPACE, "%s: workspace too small", who);
+    const ViewParams k{(int32_t)vp.pad_len, (int32_t)vp.crop_len, (int32_t)vp.final_len, vp.stages, vp.train, vp.zero_mean,
+                       vp.has_padding_value, vp.padding_value, (uint32_t)(vp.seed & 0xFFFFFFFFu), (uint32_t)(vp.seed >> 32)};
+    hipLaunchKernelGGL(view_plan_kernel, dim3((unsigned)b), dim3(VIEW_PLAN_THREADS), 0, s, wave, wave_stride, nsamples, draws, k, (ViewPlan*)workspace);
+    VIPANT_LAUNCH_CHECK();
+    return VIPANT_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t vipant_fbank_view(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, const float* window,
+                                     const float* banks, const int32_t* bank_start, const int32_t* bank_len, const int32_t* masks,
+                                     int64_t b, int64_t T, int64_t F, int32_t window_size, int32_t window_shift, int32_t nfft,
+                                     float preemphasis, float norm_mean, float norm_std, vipant_view_params view, const double* draws,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    VIPANT_REQUIRE(b > 0 && b < 65536 && T > 0 && F > 0 && F <= 256, VIPANT_EBADSHAPE, "fbank_view: bad batch b=%ld T=%ld F=%ld", (long)b, (long)T, (long)F);
+    VIPANT_REQUIRE(nfft == 512 || nfft == 1024 || nfft == 2048, VIPANT_EBADSHAPE, "fbank_view: padded window %d not in {512, 1024, 2048}", nfft);
+    VIPANT_REQUIRE(window_size > 1 && window_size <= nfft && window_size > nfft / 2 && window_shift > 0, VIPANT_EBADSHAPE,
+                   "fbank_view: bad window %d / shift %d for padded size %d", window_size, window_shift, nfft);
+    VIPANT_REQUIRE(out != nullptr && window != nullptr && banks != nullptr && bank_start != nullptr && bank_len != nullptr, VIPANT_EBADSHAPE,
+                   "fbank_view: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t rc = launch_view_plan("fbank_view", wave, wave_stride, nsamples, b, view, draws, workspace, workspace_bytes, s);
+    if (rc != VIPANT_OK) return rc;
+    FbankArgs a{wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, nullptr, {nullptr}, nullptr, nullptr,
+                (int)T, (int)F, window_size, window_shift, preemphasis, norm_mean, norm_std};
+    a.plan = (const ViewPlan*)workspace;
+    switch (nfft) {
+        case 512: return launch_fbank<512, MODE_VIEW>(a, b, s);
+        case 1024: return launch_fbank<1024, MODE_VIEW>(a, b, s);
+        default: return launch_fbank<2048, MODE_VIEW>(a, b, s);
+    }
+}
+
+extern "C" int32_t vipant_wave_view(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* wave_out, int64_t out_stride,
+                                    int64_t* nsamples_out, int64_t b, vipant_view_params view, const double* draws, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    VIPANT_REQUIRE(wave_out != nullptr && nsamples_out != nullptr && out_stride > 0 && out_stride < (int64_t)1 << 31, VIPANT_EBADSHAPE,
+                   "wave_view: bad output (stride %ld)", (long)out_stride);
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t rc = launch_view_plan("wave_view", wave, wave_stride, nsamples, b, view, draws, workspace, workspace_bytes, s);
+    if (rc != VIPANT_OK) return rc;
+    const int64_t blocks = ceil_div(b * out_stride, 256);
+    hipLaunchKernelGGL(wave_view_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, wave, wave_stride,
+                       (const ViewPlan*)workspace, wave_out, out_stride, nsamples_out, b);
+    VIPANT_LAUNCH_CHECK();
+    return VIPANT_OK;
 }

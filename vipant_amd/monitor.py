@@ -764,7 +764,10 @@ class ASMonitor(Monitor):
     eval and checkpoint are the base trainer's.  What differs is the batch: waveform batches go through the GPU front-end
     (vipant_amd/frontend.py) inside `make_batch`, and when training with `running.mixup_rate > 0` the clips are mixed in the
     front-end's launch with partners from the same batch (the reference draws the partner from the dataset in a loader worker)
-    and the labels become lam y + (1 - lam) y[partner], which BCELossHead scores as fractions (`soft_targets`).
+    and the labels become lam y + (1 - lam) y[partner], which BCELossHead scores as fractions (`soft_targets`).  Without mixup
+    (`running.clf=False`, or `mixup_rate` 0) the batch takes the reference's other branch: the `running.audio.audio_transforms`
+    chain when `transform_audio` is on and the model is training, and the crop rule for clips longer than the front-end's
+    `crop_len`, both inside the front-end's launch (`KaldiFbank.draw_views`, `view=`).
     `eval=True running.zero_shot=True` scores the clips against one prompt per class through the text tower."""
     with_text = False
     partial_head_grads = True
@@ -831,12 +834,19 @@ class ASMonitor(Monitor):
             train = self.model.training
             fbank = self.frontend(train)
             nsamples = torch.as_tensor(batch[2]).to(self.device, non_blocking=True)
-            mix = None
-            if train and self.mixup_rate > 0:
-                mix = fbank.draw_mixup(audios.shape[0], self.mixup_rate, self.aug_generator)
-                labels = self.soft_labels(labels, *mix)
+            mix = view = None
+            if self.mixup_rate > 0 and self.cfg.running.get("clf", True):      # the clf loader: mixup (audioset_cls.py:374-400)
+                if train:
+                    mix = fbank.draw_mixup(audios.shape[0], self.mixup_rate, self.aug_generator)
+                    labels = self.soft_labels(labels, *mix)
+            else:                                                              # the cst loader: waveform transforms + crop rule (:402-432)
+                crop = int(torch.as_tensor(batch[2]).max()) > fbank.crop_len   # (the host's copy of the lengths: no device sync)
+                if train and (fbank.chain or crop):
+                    view = fbank.draw_views(audios.shape[0], self.aug_generator)
+                elif crop:
+                    view = True                                                # evaluation: the centred window and its rule
             masks = fbank.draw_masks(audios.shape[0], self.aug_generator) if train else None
-            audios = fbank(audios.float(), nsamples, masks=masks, mix=mix)
+            audios = fbank(audios.float(), nsamples, masks=masks, mix=mix, view=view)
         else:
             audios = audios.unsqueeze(1)
         return images, audios, None, labels, batch[-1]
