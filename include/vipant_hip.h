@@ -438,6 +438,51 @@ int32_t vipant_wave_view(const float* wave, int64_t wave_stride, const int64_t* 
                          int64_t* nsamples_out, int64_t b, vipant_view_params view, const double* draws, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- image views (vipant_amd/csrc/image.hip): the image towers' input stage --------------------------------
+ * Decoded uint8 frames in, normalised fp32 [b, 3, n, n] out: what the reference's loaders do per frame in PIL
+ * (cvap/data/image/transform.py:11-18 make_clip_image_transform, :146-200 BarlowImageTransform; image_audio.py:117, 170-171, 232-237).
+ * frames uint8 [b, max_h, max_w, 3] on the device with element strides (stride_b, stride_h, stride_w, 1); frame i occupies the top
+ * left hw[i] = (h, w) pixels, the rest is padding nobody reads.  hw int32 [b, 2] and draws fp64 [b, 16] are HOST arrays (the loader
+ * that decoded the frames knows both): every refusal is made on the host before anything is written, and the launch copies them
+ * into the workspace on `stream` (from pageable memory such a copy cannot be captured into a graph; the caller keeps both arrays
+ * alive until the stream has passed the call).
+ *   draws = NULL: the `clip` chain.  Resize(n) (shorter side to n, longer to int(n * long / short)) + CenterCrop(n) (offset
+ *            int(round((size - n) / 2.0)), half to even); only the output pixels inside the crop are computed, with the
+ *            coefficients of the full resize.
+ *   draws[i] = (box top, left, height, width; flip; the order of the four jitter operations 0 brightness, 1 contrast,
+ *            2 saturation, 3 hue, or -1 for "no jitter"; their four factors in that numbering; gray; sigma, 0 = no blur; solarise):
+ *            the integer box is cut from the frame and resampled to n x n, then flipped horizontally, jittered, turned gray,
+ *            blurred and solarised as the row says.  params.chain (VIPANT_IMAGE_*) enables each stage for the whole batch.
+ * The resample is PIL's Image.resize(BICUBIC) byte for byte: two separable passes, horizontal first, uint8 in between; per output
+ * index scale = in / out, fs = max(scale, 1), support = 2 fs, center = (i + 0.5) scale, xmin = max(0, int(center - support + 0.5)),
+ * xmax = min(in, int(center + support + 0.5)), weights bicubic((x - center + 0.5) / fs) (a = -0.5) normalised by their sum in double,
+ * k = int(w 2^22 +- 0.5), result clip8((2^21 + sum k pixel) >> 22).  The photometric stages run on fp32 code values in [0, 255] and
+ * nothing is quantised between them: L = floor((19595 r + 38470 g + 7471 b) / 65536 + 0.5) (PIL's convert("L")); brightness,
+ * contrast, saturation = clip(deg + factor (x - deg)) with deg = 0, floor(mean(L) + 0.5), L (PIL's ImageEnhance); hue = colorsys
+ * rgb -> hsv, h = frac(h + factor), -> rgb; blur = PIL's GaussianBlur(sigma): three extended box passes along the rows, then three
+ * along the columns, clamp to the edge (s2 = sigma^2 / 3, L = sqrt(12 s2 + 1), l = floor((L - 1) / 2),
+ * a = (2l + 1)(l (l + 1) - 3 s2) / (6 (s2 - (l + 1)^2)), a pass = (inner 2l + 1 taps + a (the two outer taps)) / (2 (l + a) + 1));
+ * a jitter operation whose factor is neutral (1, hue: 0) is skipped;
+ * solarise = x >= 128 -> 255 - x; last ((x / 255) - mean) / std as three rounded fp32 operations.  The same input gives the same bits
+ * on every run and in every batch.
+ * Limits: n <= 224, and per axis a source extent (the frame's side for `clip`, the box's otherwise) of at most 8 times the resized
+ * extent.  Refused with VIPANT_EBADSHAPE, nothing written: a frame or box beyond that, h or w < 1 or beyond max_h / max_w, a box that
+ * is not an integer box inside its frame, a jitter order that is no permutation, a NULL argument (draws excepted), b < 1. */
+#define VIPANT_IMAGE_FLIP 1
+#define VIPANT_IMAGE_JITTER 2
+#define VIPANT_IMAGE_GRAY 4
+#define VIPANT_IMAGE_BLUR 8
+#define VIPANT_IMAGE_SOLARISE 16
+typedef struct vipant_image_params {
+    int32_t n;
+    float mean[3], std[3];
+    int32_t chain;
+} vipant_image_params;
+size_t vipant_image_view_workspace_bytes(int64_t b, int64_t n, int64_t max_h, int64_t max_w);
+int32_t vipant_image_view(const uint8_t* frames, int64_t stride_b, int64_t stride_h, int64_t stride_w, int64_t max_h, int64_t max_w,
+                          const int32_t* hw, const double* draws, vipant_image_params params, float* out, int64_t b,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LARS (cvap/module/lars.py:43-72), one fused pass per tensor list ---------------------------------
  * For tensor i (n[i] elements): dp = g + wd*p (adapt[i]); q = eta*|p|/|dp| (adapt[i], both norms > 0);
  * mu = momentum*mu + q*dp; p -= lr[i]*mu.  ptrs are device arrays of device pointers. */

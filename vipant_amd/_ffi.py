@@ -45,6 +45,14 @@ class ViewParams(C.Structure):
                 ("has_padding_value", _i32), ("train", _i32), ("zero_mean", _i32), ("stages", _i32), ("reserved", _i32)]
 
 
+IMAGE_FLIP, IMAGE_JITTER, IMAGE_GRAY, IMAGE_BLUR, IMAGE_SOLARISE = 1, 2, 4, 8, 16     # VIPANT_IMAGE_*
+
+
+class ImageParams(C.Structure):
+    """struct vipant_image_params (include/vipant_hip.h): the static parameters of vipant_image_view, by value."""
+    _fields_ = [("n", _i32), ("mean", _f32 * 3), ("std", _f32 * 3), ("chain", _i32)]
+
+
 # name -> (restype, argtypes); mirrors include/vipant_hip.h one to one
 PROTOTYPES = {
     "vipant_last_error": (C.c_char_p, []),
@@ -112,6 +120,8 @@ PROTOTYPES = {
     "vipant_fbank_view_workspace_bytes": (_sz, [_i64]),
     "vipant_fbank_view": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, ViewParams, _p, _p, _sz, _p]),
     "vipant_wave_view": (_i32, [_p, _i64, _p, _p, _i64, _p, _i64, ViewParams, _p, _p, _sz, _p]),
+    "vipant_image_view_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "vipant_image_view": (_i32, [_p, _i64, _i64, _i64, _i64, _i64, _p, _p, ImageParams, _p, _i64, _p, _sz, _p]),
     # fused operator set (vipant_amd/csrc/block.hip)
     "vipant_block_workspace_bytes": (_sz, [_i64, _i64]),
     "vipant_ln_qkv_fwd": (_i32, [_p] * 11 + [_i64, _i64, _p, _i32, _p]),

@@ -35,7 +35,10 @@ class SyntheticLoader:
     N x batch_size samples and keeps its contiguous chunk.
     `running.multi_view` (configs/running/siamese.yaml): the five-slot batch of the siamese VA trainer instead -- (prime image
     features [b, E], image view 1, image view 2 [b, 3, res, res], audio view 1, audio view 2 [b, T, F], names); the two views of a
-    modality are one clip under independent noise."""
+    modality are one clip under independent noise.
+    `running.image_frames: [H, W]` (opt-in): the image slot holds decoded FRAMES uint8 [b, H, W, 3] instead, as a loader that
+    leaves the image transform to the device yields them (vipant_amd/image_views.py); under `multi_view` the same frames fill both
+    view slots -- one frame gives two views, as in the reference (cvap/data/image_audio.py:232-237)."""
 
     def __init__(self, cfg, steps, with_text, device_rank=0):
         self.cfg, self.steps, self.with_text, self.rank = cfg, int(steps), with_text, device_rank
@@ -50,6 +53,12 @@ class SyntheticLoader:
         self.res = int(cfg.running.resolution) if not isinstance(cfg.running.resolution, (list, tuple)) else 224
         self.embed = int(cfg.running.embed_dim)
         self.multi_view = bool(rcfg.get("multi_view", False))
+        frames = rcfg.get("image_frames", None)
+        self.image_frames = (int(frames[0]), int(frames[1])) if frames else None
+
+    def _frames(self, step):
+        g = torch.Generator().manual_seed(77003 + 1000 * self.rank + step)      # a generator of their own: the other slots keep their draws
+        return torch.randint(0, 256, (self.b, *self.image_frames, 3), generator=g, dtype=torch.uint8)
 
     def __len__(self):
         return self.steps
@@ -63,6 +72,9 @@ class SyntheticLoader:
                 batch = (torch.randn(self.b, self.embed, generator=g),
                          frames + 0.5 * torch.randn(frames.shape, generator=g), frames + 0.5 * torch.randn(frames.shape, generator=g),
                          audios + 0.5 * torch.randn(audios.shape, generator=g), audios + 0.5 * torch.randn(audios.shape, generator=g))
+                if self.image_frames:
+                    u8 = self._frames(step)
+                    batch = (batch[0], u8, u8, batch[3], batch[4])
                 names = [f"synthetic-{self.rank}-{step}-{i}" for i in range(self.b)]
                 if self.chunk is not None:
                     sl = slice(self.chunk[0] * self.chunk[1], (self.chunk[0] + 1) * self.chunk[1])
@@ -83,6 +95,8 @@ class SyntheticLoader:
                 images = (torch.randn(self.b, self.embed, generator=g) if self.precomputed
                           else torch.randn(self.b, 3, self.res, self.res, generator=g))
                 text = torch.zeros(self.b, 1, dtype=torch.int64)
+                if self.image_frames and not self.precomputed:
+                    images = self._frames(step)
             labels = torch.zeros(self.b, dtype=torch.int64)
             names = [f"synthetic-{self.rank}-{step}-{i}" for i in range(self.b)]
             if self.chunk is not None:
@@ -177,8 +191,30 @@ class Monitor(object):
             self.epoch(iepoch)
 
     # ------------------------------------------------------------------ cvalp.py:136-154
+    def image_views(self, images, which="prime", siamese=False):
+        """A uint8 image slot [b, H, W, 3] (decoded frames) -> the tower's input, on the device (vipant_amd/image_views.py): `clip`
+        unless this is a training view of the siamese trainer without `running.clip_tf`; then `barlow`, with its draws from the
+        per-rank host generator, consumed in step order.  Anything else passes through."""
+        if images is None or images.dtype != torch.uint8 or images.dim() != 4:
+            return images
+        from .image_views import ImageViews
+        cache = self.__dict__.setdefault("_image_views", {})
+        key = (bool(self.model.training), which, siamese)
+        if key not in cache:
+            cache[key] = ImageViews.from_config(self.cfg.running, train=key[0], which=which, device=self.device, siamese=siamese)
+        iv = cache[key]
+        if iv.chain == "clip":
+            return iv(images)
+        if "_image_generator" not in self.__dict__:
+            self._image_generator = self._image_views_generator()
+        hw = [[images.shape[1], images.shape[2]]] * images.shape[0]
+        return iv(images, draws=iv.draw_image_views(hw, self._image_generator))
+
+    def _image_views_generator(self):
+        return torch.Generator().manual_seed(int(self.cfg.seed) + 11 + 1000 * max(int(self.cfg.rank), 0))
+
     def make_batch(self, batch):
-        images = torch.as_tensor(batch[0]).to(self.device, non_blocking=True)
+        images = self.image_views(torch.as_tensor(batch[0]).to(self.device, non_blocking=True))
         audios = torch.as_tensor(batch[1]).to(self.device, non_blocking=True).unsqueeze(1)
         text = torch.as_tensor(batch[2]).to(self.device, non_blocking=True)
         labels = torch.as_tensor(batch[3]).to(self.device, non_blocking=True)
@@ -412,7 +448,8 @@ class VASMonitor(Monitor):
     """Siamese multi-view VA trainer (cvap/monitor/siamese_va.py:19-180; `monitor=VASMonitor worker=CVASP +running=siamese`).  The
     epoch loop is the base trainer's; what differs is the batch -- five slots, of which only the views that a live pair of
     `model.loss` reads are moved to the device, image views rescaled bilinearly to `running.resolution` -- and the worker's
-    signature."""
+    signature.  View slots that hold uint8 frames (`running.image_frames`) become the prime and the second `barlow` view of
+    vipant_amd/image_views.py instead (`clip` under `running.clip_tf` and at evaluation); the second only when `model.loss.vv`."""
     with_text = False
 
     def make_batch(self, batch):
@@ -426,8 +463,8 @@ class VASMonitor(Monitor):
                 images = torch.nn.functional.interpolate(images, res, mode="bilinear", align_corners=False)
             return images
         images = to_dev(batch[0]) if lcfg.vp or lcfg.ap else None
-        images_v1 = scale_images(to_dev(batch[1]))
-        images_v2 = scale_images(to_dev(batch[2])) if lcfg.vv else None
+        images_v1 = scale_images(self.image_views(to_dev(batch[1]), "prime", siamese=True))
+        images_v2 = scale_images(self.image_views(to_dev(batch[2]), "second", siamese=True)) if lcfg.vv else None
         audios_v1 = to_dev(batch[3]).unsqueeze(1)
         audios_v2 = to_dev(batch[4]).unsqueeze(1) if lcfg.aa else None
         return images, images_v1, images_v2, audios_v1, audios_v2, batch[-1]
@@ -824,7 +861,7 @@ class ASMonitor(Monitor):
 
     # ------------------------------------------------------------------ audioset_clf.py:192-210
     def make_batch(self, batch):
-        images = torch.as_tensor(batch[0]).to(self.device, non_blocking=True)
+        images = self.image_views(torch.as_tensor(batch[0]).to(self.device, non_blocking=True))
         audios = torch.as_tensor(batch[1]).to(self.device, non_blocking=True)
         labels = torch.as_tensor(batch[3]).to(self.device, non_blocking=True)
         res = self.cfg.running.resolution
