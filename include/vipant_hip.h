@@ -438,6 +438,24 @@ int32_t vipant_wave_view(const float* wave, int64_t wave_stride, const int64_t* 
                          int64_t* nsamples_out, int64_t b, vipant_view_params view, const double* draws, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- PCM ingest (vipant_amd/csrc/pcm.hip): decoded 16-bit PCM -> the fp32 mono waveform of the front-end ----
+ * What torchaudio.load(normalize=True) and the head of _extract_kaldi_spectrogram (cvap/data/audio/transform.py:15-21) compute per
+ * file, for a ragged batch in one launch.  pcm int16 [b, pcm_stride] on the device: clip i holds nframes[i] frames of channels[i]
+ * interleaved samples; nframes int64 [b] and channels int32 [b] are DEVICE arrays.  wave fp32 [b, wave_stride], nsamples_out int64 [b].
+ *   VIPANT_PCM_FIRST  w[j] = pcm[j ch] * 2^-15 (channel 0: what kaldi.fbank takes when mean_channel is off, image_audio.py)
+ *   VIPANT_PCM_MEAN   w[j] = (float(sum_c pcm[j ch + c]) * 2^-15) / float(ch): int32 sum, exact product, one IEEE fp32 division --
+ *                     the bits of torch's (x.float() / 32768).mean(0) on the CPU
+ * tile_len > 0 and 0 < n < tile_len: the clip is repeated to n * ceil(tile_len / n) samples (the reference's slice after torch.tile
+ * truncates nothing).  A length above wave_stride is clamped to it.  nsamples_out[i] = the resulting length; wave[i, j] = 0 from there
+ * to wave_stride; nothing outside [b, wave_stride] is written.  The host cannot see the device values: channels[i] is clamped into
+ * [1, 8] before any use and nframes[i] into [0, pcm_stride / channels], so nothing outside a clip's row of pcm is read.
+ * Refused with VIPANT_EBADSHAPE before any launch, nothing written: a NULL argument, b < 1, a stride < 1, tile_len < 0, an unknown mode.
+ * No workspace; the same input gives the same bits on every run. */
+#define VIPANT_PCM_FIRST 0
+#define VIPANT_PCM_MEAN 1
+int32_t vipant_pcm_wave(const int16_t* pcm, int64_t pcm_stride, const int64_t* nframes, const int32_t* channels, int32_t mode,
+                        int64_t tile_len, float* wave, int64_t wave_stride, int64_t* nsamples_out, int64_t b, void* stream);
+
 /* ---- image views (vipant_amd/csrc/image.hip): the image towers' input stage --------------------------------
  * Decoded uint8 frames in, normalised fp32 [b, 3, n, n] out: what the reference's loaders do per frame in PIL
  * (cvap/data/image/transform.py:11-18 make_clip_image_transform, :146-200 BarlowImageTransform; image_audio.py:117, 170-171, 232-237).

@@ -14,6 +14,8 @@ from typing import Optional
 # torch then reports "No HIP GPUs are available".
 import torch  # noqa: F401
 
+from .errors import VipantError  # noqa: F401  (defined apart, so that host-only code can raise it without loading this module)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIPANT_HIP_LIB") or os.path.join(_HERE, "lib", "libvipant_hip.so")   # override: A/B timing of builds
 ABI_VERSION = 101             # what vipant_version() of a library with the argument lists of PROTOTYPES returns
@@ -46,6 +48,7 @@ class ViewParams(C.Structure):
 
 
 IMAGE_FLIP, IMAGE_JITTER, IMAGE_GRAY, IMAGE_BLUR, IMAGE_SOLARISE = 1, 2, 4, 8, 16     # VIPANT_IMAGE_*
+PCM_FIRST, PCM_MEAN = 0, 1                                                          # VIPANT_PCM_*
 
 
 class ImageParams(C.Structure):
@@ -120,6 +123,7 @@ PROTOTYPES = {
     "vipant_fbank_view_workspace_bytes": (_sz, [_i64]),
     "vipant_fbank_view": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, ViewParams, _p, _p, _sz, _p]),
     "vipant_wave_view": (_i32, [_p, _i64, _p, _p, _i64, _p, _i64, ViewParams, _p, _p, _sz, _p]),
+    "vipant_pcm_wave": (_i32, [_p, _i64, _p, _p, _i32, _i64, _p, _i64, _p, _i64, _p]),
     "vipant_image_view_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "vipant_image_view": (_i32, [_p, _i64, _i64, _i64, _i64, _i64, _p, _p, ImageParams, _p, _i64, _p, _sz, _p]),
     # fused operator set (vipant_amd/csrc/block.hip)
@@ -152,10 +156,6 @@ PROTOTYPES = {
     "vipant_bce_logits": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
     "vipant_bce_logits_soft": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
 }
-
-
-class VipantError(RuntimeError):
-    pass
 
 
 _lib: Optional[C.CDLL] = None

@@ -22,6 +22,8 @@ _running_common = {
     "embed_dim": "${model.image.embed_dim}", "resolution": "${model.image.resolution}",
     "max_audio_len": "${running.audio.max_len}", "num_mel_bins": "${running.audio.num_mel_bins}",
     "train_samples": 1.0, "test_samples": 5000,
+    # the rate every clip of a `data_root` dataset must have (vipant_amd/data: one batched filter-bank launch has one rate)
+    "sample_rate": 16000,
     # dataset-free operation (this build): synthetic spectrogram / token batches, SURVEY.md 8-D2
     "synthetic": True, "synthetic_steps": 8, "precomputed_image": False,
     # activation-memory plan for batches that do not fit: towers in micro-batches under one global-batch loss,
@@ -81,6 +83,8 @@ GROUPS = {
             "frame_shift": 10, "htk_compat": True, "use_energy": False, "window_type": "hanning", "num_mel_bins": 128,
             "zero_mean_wf": True, "transform_audio": False, "audio_transforms": [], "transform_fbank": True,
             "fbank_transforms": [["FrequencyMasking", [32]], ["TimeMasking", [200]]],
+            # which channel of a multi-channel clip the waveform is (frontend.pcm_wave): first (the reference's) | mean
+            "channel": "first",
         },
     },
     "model/image": {

@@ -4,7 +4,8 @@ The reference computes one Kaldi filter bank per clip on CPU dataloader workers
 (cvap/data/audio/transform.py:12-35, parameters cvap/data/image_audio.py:119-126), pads / normalises it and applies
 SpecAugment masks (image_audio.py:183-207, configs/running/audio/default.yaml).  `KaldiFbank` does the same for a whole
 batch of device-resident waveforms in two launches (`vipant_fbank`; three with waveform mixup, `vipant_fbank_mix`) and returns the [b, 1, T, F] tensor
-`ViTPreEncoder` takes.  File decoding and resampling stay with the loader.
+`ViTPreEncoder` takes.  File decoding stays with the loader (vipant_amd/data); `pcm_wave` turns the 16-bit PCM it decodes into
+those waveforms in one launch (`vipant_pcm_wave`: int16 -> fp32, the channel rule, `tile_audio`).  There is no resampling.
 
 What the reference does to the waveform in front of the filter bank (transform.py:22-28) happens inside the launch as well
 (`vipant_fbank_view`): the `running.audio.audio_transforms` chain of transform.py:75-202 -- any subsequence of RandomFlip,
@@ -104,6 +105,45 @@ def parse_audio_transforms(transforms) -> dict:
             raise _chain_error(f"{name}(train=False) is not supported")
         chain[name] = args
     return chain
+
+
+PCM_MODES = {"first": _ffi.PCM_FIRST, "mean": _ffi.PCM_MEAN}
+PCM_MAX_CHANNELS = 8
+
+
+def pcm_wave(pcm: torch.Tensor, nframes: torch.Tensor, channels: torch.Tensor, mode: str = "first", tile_len: int = 0,
+             wave_stride: Optional[int] = None):
+    """Decoded 16-bit PCM -> the waveforms `KaldiFbank.__call__(wave, nsamples, ...)` takes, in one launch (`vipant_pcm_wave`):
+    what torchaudio.load(normalize=True) and the head of _extract_kaldi_spectrogram (transform.py:15-21) do per file.
+    pcm int16 [b, stride] on the device, clip i = nframes[i] frames of channels[i] interleaved samples (int64 / int32 [b]; they are
+    moved to the device, and nobody waits for them).  mode `first`: channel 0 (what kaldi.fbank takes); `mean`: the channel mean,
+    with torch's CPU bits.  tile_len > 0: a clip shorter than tile_len is repeated to n * ceil(tile_len / n) samples
+    (`running.audio.tile_audio`).  wave_stride: the width of the result (a longer clip is cut to it); default: the longest clip
+    `stride` can hold, or twice tile_len where tiling can exceed that.  -> (wave fp32 [b, wave_stride], zero beyond a clip's length;
+    nsamples int64 [b])."""
+    if not isinstance(pcm, torch.Tensor) or not pcm.is_cuda:
+        raise VipantError("pcm_wave: pcm must be a device tensor (there is no CPU path)")
+    if pcm.dtype != torch.int16 or pcm.dim() != 2:
+        raise VipantError(f"pcm_wave: pcm must be a 2-d int16 tensor, got {pcm.dtype} {tuple(pcm.shape)}")
+    if mode not in PCM_MODES:
+        raise VipantError(f"pcm_wave: mode `{mode}' is not one of {', '.join(PCM_MODES)}")
+    pcm = pcm.contiguous()
+    b, stride = pcm.shape
+    dev = pcm.device
+    nframes = torch.as_tensor(nframes).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+    channels = torch.as_tensor(channels).to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
+    if nframes.shape != (b,) or channels.shape != (b,):
+        raise VipantError(f"pcm_wave: nframes / channels must have shape [{b}], got {tuple(nframes.shape)} / {tuple(channels.shape)}")
+    tile_len = int(tile_len)
+    if wave_stride is None:
+        wave_stride = max(int(stride), 1)
+        if 0 < tile_len and stride < 2 * tile_len:          # a tiled clip has fewer than 2 tile_len samples
+            wave_stride = max(2 * tile_len - 2, wave_stride)
+    wave = torch.empty((b, int(wave_stride)), dtype=F32, device=dev)
+    nsamples = torch.empty((b,), dtype=torch.int64, device=dev)
+    call("vipant_pcm_wave", pcm.data_ptr(), stride, nframes.data_ptr(), channels.data_ptr(), PCM_MODES[mode], tile_len,
+         wave.data_ptr(), int(wave_stride), nsamples.data_ptr(), b, ops._stream())
+    return wave, nsamples
 
 
 class KaldiFbank:

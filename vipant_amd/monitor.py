@@ -8,8 +8,11 @@ Deliberate deviations (documented in DESIGN.md):
     fp16 autocast + GradScaler pair (cvalp.py:123, 201-205) has no counterpart here;
   * one process per GPU: `mode=ddp` is served by vipant_amd.parallel (feature all-gather + bucketed gradient
     all-reduce); the reference's ddp branch cannot start (train.py:35 names an undefined Monitor);
-  * the reference's dataset builders (cvap/data/*) are outside the hot-path scope; batches come from a synthetic
-    loader with the same tensor contract unless a loader is injected through `dataloader=`.
+  * with `running.data_root` empty (the default) batches come from a synthetic loader with the reference's tensor contract,
+    unless a loader is injected through `dataloader=`.  With `running.data_root=DIR` the bimodal VA trainer reads the reference's
+    raw-file image-audio dataset (vipant_amd/data, cvap/data/image_audio.py:90-222): loader workers decode containers only, and
+    `make_batch` runs waveform, log-mel, augmentation and image transform on the device; the reference's
+    other dataset builders are not built.
 """
 from __future__ import annotations
 
@@ -21,6 +24,8 @@ import numpy as np
 import torch
 
 from . import parallel
+from ._ffi import VipantError
+from .data import FrameBatch, PcmBatch
 from .model import build_main_model
 from .module import LARS, adjust_learning_rate, exclude_bias_or_norm
 
@@ -119,12 +124,19 @@ def _synthetic_prompts(seed, nclass):
 class Monitor(object):
     with_text = True      # VALMonitor (AT); VAMonitor sets False
     partial_head_grads = False      # a classification head scores a rank's own rows: its gradients join the replica reduction
+    norms_only = False              # `running.audio.eval_norms` on a file dataset: the statistics are the run's only task
 
     def __init__(self, cfg, echo, device, dataloader=None):
         self.cfg, self.echo, self.device = cfg, echo, device
-        self.dataloader = dataloader if dataloader is not None else self.build_data()
         self.evalloader = self.testloader = None
         self.gold_file = None
+        self.model = None
+        self.dataloader = dataloader if dataloader is not None else self.build_data()
+        acfg = cfg.running.get("audio", None) or {}
+        self.norms_only = dataloader is None and self._from_files() and bool(acfg.get("eval_norms", False))
+        if self.norms_only:
+            self.eval_norms()
+            return      # mean & std of the data: the only task of such a run (cvap.py:28-30)
         model = build_main_model(cfg, echo)
         negatives = cfg.running.get("negatives", "global")
         tunable_params = model.build(negatives=negatives)
@@ -166,15 +178,64 @@ class Monitor(object):
             if model.audio_head is not None and hasattr(model.audio_head, "encoder"):
                 model.audio_head.encoder.fp8 = True
 
+    def _from_files(self):
+        return bool(self.cfg.running.get("data_root", "") or "")
+
     def build_data(self):
         rcfg = self.cfg.running
+        if self._from_files():
+            return self.build_file_data()
         steps = rcfg.get("synthetic_steps", 8)
         loader = SyntheticLoader(self.cfg, steps, self.with_text, max(self.cfg.rank, 0))
         self.echo(f"Instantiate main dataloader from `synthetic': total {len(loader)} batches.")
         return loader
 
+    # ------------------------------------------------------------------ cvap.py:67-87
+    def build_file_data(self):
+        """`running.data_root=DIR`: the raw-file image-audio dataset, and when training the evaluation loader if its index exists."""
+        from .data import build_image_audio_dataloader
+        rcfg = self.cfg.running
+        if self.with_text:
+            raise VipantError("running.data_root: the audio-text dataset is not built (the image-audio dataset serves monitor=VAMonitor)")
+        data_name = rcfg.eval_name if self.cfg.eval else rcfg.data_name
+        _, loader = build_image_audio_dataloader(self.cfg, data_name, shuffle=(not self.cfg.eval), train=(not self.cfg.eval))
+        nstep = len(loader)
+        if nstep < rcfg.peep_rate:
+            rcfg.peep_rate = nstep
+        self.echo(f"Instantiate main dataloader from `{data_name}': total {nstep} ({rcfg.peep_rate}) batches.")
+        self.gold_file = f"{rcfg.data_root}/{data_name}.csv"
+        eval_name = "" if self.cfg.eval else rcfg.eval_name
+        if eval_name and os.path.isfile(f"{rcfg.data_root}/{eval_name}.csv"):
+            _, self.evalloader = build_image_audio_dataloader(self.cfg, eval_name, shuffle=False, train=False)
+            self.echo(f"Will do evaluation every {rcfg.save_rate} steps on {len(self.evalloader)} batches.")
+            self.gold_file = f"{rcfg.data_root}/{eval_name}.csv"
+        return loader
+
+    # ------------------------------------------------------------------ cvap.py:43-65
+    def eval_norms(self):
+        """`running.audio.eval_norms=True`: mean and standard deviation of the main loader's log-mels, norms and every augmentation
+        off (KaldiFbank.from_config switches them off under the key) -- the `running.audio.norms` of a new dataset.  Per clip the
+        mean and the mean square over [T, F], in float64; then their means over the clips."""
+        self.echo("Evaluate mean and std...")
+        som_list, sos_list = [], []
+        for step, batch in enumerate(self.dataloader):
+            audios = self.make_batch(batch)[1].double()
+            som_list.append(audios.mean(dim=[2, 3]))
+            sos_list.append((audios ** 2).mean(dim=[2, 3]))
+            self.echo(f"step {step}")
+        som = torch.cat(som_list, 0).mean(dim=[0])
+        sos = torch.cat(sos_list, 0).mean(dim=[0])
+        std = (sos - som ** 2).sqrt()
+        self.norms = (som.cpu().tolist(), std.cpu().tolist())
+        self.echo(f"MEAN: {self.norms[0]} STD: {self.norms[1]}")
+
+    def _training(self):
+        return bool(self.model.training) if self.model is not None else not self.cfg.eval
+
     # ------------------------------------------------------------------ cvalp.py:106-130
     def learn(self):
+        if self.norms_only:
+            return None
         if not self.model.training:
             self.echo("Evaluating started...")
             with torch.no_grad():
@@ -191,31 +252,81 @@ class Monitor(object):
             self.epoch(iepoch)
 
     # ------------------------------------------------------------------ cvalp.py:136-154
-    def image_views(self, images, which="prime", siamese=False):
+    def image_views(self, images, which="prime", siamese=False, hw=None):
         """A uint8 image slot [b, H, W, 3] (decoded frames) -> the tower's input, on the device (vipant_amd/image_views.py): `clip`
         unless this is a training view of the siamese trainer without `running.clip_tf`; then `barlow`, with its draws from the
-        per-rank host generator, consumed in step order.  Anything else passes through."""
+        per-rank host generator, consumed in step order.  Anything else passes through.  hw [b, 2] on the host: the (h, w) of each
+        frame inside the canvas (default: all of it)."""
         if images is None or images.dtype != torch.uint8 or images.dim() != 4:
             return images
         from .image_views import ImageViews
         cache = self.__dict__.setdefault("_image_views", {})
-        key = (bool(self.model.training), which, siamese)
+        key = (self._training(), which, siamese)
         if key not in cache:
             cache[key] = ImageViews.from_config(self.cfg.running, train=key[0], which=which, device=self.device, siamese=siamese)
         iv = cache[key]
         if iv.chain == "clip":
-            return iv(images)
+            return iv(images, hw=hw)
         if "_image_generator" not in self.__dict__:
             self._image_generator = self._image_views_generator()
-        hw = [[images.shape[1], images.shape[2]]] * images.shape[0]
-        return iv(images, draws=iv.draw_image_views(hw, self._image_generator))
+        if hw is None:
+            hw = [[images.shape[1], images.shape[2]]] * images.shape[0]
+        return iv(images, hw=hw, draws=iv.draw_image_views(hw, self._image_generator))
 
     def _image_views_generator(self):
         return torch.Generator().manual_seed(int(self.cfg.seed) + 11 + 1000 * max(int(self.cfg.rank), 0))
 
+    def _aug_generator(self):
+        """The host generator of the waveform-view and SpecAugment draws: seeded per rank, consumed in step order."""
+        return torch.Generator().manual_seed(int(self.cfg.seed) + 7 + 1000 * max(int(self.cfg.rank), 0))
+
+    def pcm_frontend(self, train, sample_rate):
+        from .frontend import KaldiFbank
+        cache = self.__dict__.setdefault("_pcm_fbank", {})
+        key = (bool(train), int(sample_rate))
+        if key not in cache:
+            cache[key] = KaldiFbank.from_config(self.cfg.running.audio, float(sample_rate), train=train, device=self.device)
+        return cache[key]
+
+    def audios_from_pcm(self, clips):
+        """A PcmBatch (decoded 16-bit clips, on the host) -> log-mels [b, 1, T, F] on the device, in the reference's order
+        (image_audio.py:183-207, transform.py:15-35): H2D, the waveform (`pcm_wave`: channel rule, `tile_audio`), then inside the
+        log-mel launch the `audio_transforms` chain and the crop rule, the filter bank, `norms`, and the SpecAugment masks.  Training
+        draws views when there is a chain or a clip longer than `crop_len`, and masks under `transform_fbank`; evaluation takes the
+        centred crop of a longer clip and nothing else; `eval_norms` switches chain, masks and norms off."""
+        from .frontend import pcm_wave
+        acfg = self.cfg.running.audio
+        train = self._training()
+        fbank = self.pcm_frontend(train, clips.sample_rate)
+        tile_len = int(fbank.max_len / 100 * clips.sample_rate) if acfg.get("tile_audio", False) else 0
+        # the lengths pcm_wave will report, from the host's copy (no device sync)
+        n = torch.minimum(clips.nframes, clips.pcm.shape[1] // clips.channels.clamp(1, 8).long()).clamp_(min=0)
+        if tile_len > 0:
+            n = torch.where((n > 0) & (n < tile_len), n * ((tile_len + n - 1) // n.clamp(min=1)), n)
+        longest = int(n.max())
+        on_dev = clips.to(self.device, non_blocking=True)
+        wave, nsamples = pcm_wave(on_dev.pcm, on_dev.nframes, on_dev.channels, mode=str(acfg.get("channel", "first")),
+                                  tile_len=tile_len, wave_stride=max(8, -(-longest // 8) * 8))
+        if "aug_generator" not in self.__dict__:
+            self.aug_generator = self._aug_generator()
+        b, view = wave.shape[0], None
+        crop = longest > fbank.crop_len
+        if train and (fbank.chain or crop):
+            view = fbank.draw_views(b, self.aug_generator)
+        elif crop:
+            view = True                                                    # evaluation: the centred window and its rule
+        masks = fbank.draw_masks(b, self.aug_generator) if train else None
+        return fbank(wave, nsamples, masks=masks, view=view)
+
     def make_batch(self, batch):
-        images = self.image_views(torch.as_tensor(batch[0]).to(self.device, non_blocking=True))
-        audios = torch.as_tensor(batch[1]).to(self.device, non_blocking=True).unsqueeze(1)
+        if isinstance(batch[0], FrameBatch):
+            images = self.image_views(batch[0].frames.to(self.device, non_blocking=True), hw=batch[0].hw)
+        else:
+            images = self.image_views(torch.as_tensor(batch[0]).to(self.device, non_blocking=True))
+        if isinstance(batch[1], PcmBatch):
+            audios = self.audios_from_pcm(batch[1])
+        else:
+            audios = torch.as_tensor(batch[1]).to(self.device, non_blocking=True).unsqueeze(1)
         text = torch.as_tensor(batch[2]).to(self.device, non_blocking=True)
         labels = torch.as_tensor(batch[3]).to(self.device, non_blocking=True)
         return images, audios, text, labels, batch[-1]
@@ -321,6 +432,9 @@ class Monitor(object):
         nchunk = parallel.world_size()
         ocfg = self.cfg.optimizer
         warmup_step_rate = max(int(ocfg.warmup_steps) // 20, 1)      # cvalp.py:177
+        for part in (getattr(self.dataloader, "dataset", None), getattr(self.dataloader, "sampler", None)):
+            if hasattr(part, "set_epoch"):          # a file dataset's per-item draws and a DistributedSampler's order (cvap.py:107-108)
+                part.set_epoch(iepoch)
         for step, batch in enumerate(self.dataloader, start=iepoch * len(self.dataloader)):
             inputs, ninst = self._step_inputs(self.make_batch(batch))
             self.timeit(all_time, key="data")
