@@ -434,6 +434,21 @@ int32_t vipant_fbank_view(const float* wave, int64_t wave_stride, const int64_t*
                           int64_t b, int64_t T, int64_t F, int32_t window_size, int32_t window_shift, int32_t nfft,
                           float preemphasis, float norm_mean, float norm_std, vipant_view_params view, const double* draws,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* Two masked views of ONE filter-bank evaluation: what the siamese dataset's FbankTransform returns (cvap/data/audio/transform.py:223-258,
+ * called at cvap/data/image_audio.py:256-285) -- the same log-mel under two SpecAugment mask sets.  Arguments, vipant_view_params, draws
+ * and workspace are vipant_fbank_view's; out / masks belong to the first view and out2 / masks2 to the second, each fp32 [b, T, F] /
+ * int32 [b, 4] (f0, f1, t0, t1), either mask NULL = no mask for that view.  One plan launch, one filter-bank launch.  Per view and row:
+ * a live row (inside the clip's frames and outside that view's time mask) holds the value, 0 under that view's frequency mask; a row
+ * inside that view's time mask holds 0; a row beyond the clip's frames holds the padding value, 0 under that view's frequency mask.
+ * out has the bits of vipant_fbank_view(masks) and out2 those of vipant_fbank_view(masks2) for the same draws: a pair of frames that
+ * is live alike in both views is transformed once and stored twice; where a time-mask edge of one view splits a pair, each view gets
+ * a transform with exactly its own live frames (at most four such pairs per clip).  Every element of both outputs is written once.
+ * out2 NULL, or out2 overlapping out, is refused before any launch, as is everything vipant_fbank_view refuses. */
+int32_t vipant_fbank_view_pair(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, float* out2,
+                               const float* window, const float* banks, const int32_t* bank_start, const int32_t* bank_len,
+                               const int32_t* masks, const int32_t* masks2, int64_t b, int64_t T, int64_t F, int32_t window_size,
+                               int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean, float norm_std,
+                               vipant_view_params view, const double* draws, void* workspace, size_t workspace_bytes, void* stream);
 int32_t vipant_wave_view(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* wave_out, int64_t out_stride,
                          int64_t* nsamples_out, int64_t b, vipant_view_params view, const double* draws, void* workspace,
                          size_t workspace_bytes, void* stream);

@@ -122,6 +122,7 @@ PROTOTYPES = {
     "vipant_fbank_mix": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _p, _sz, _p]),
     "vipant_fbank_view_workspace_bytes": (_sz, [_i64]),
     "vipant_fbank_view": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, ViewParams, _p, _p, _sz, _p]),
+    "vipant_fbank_view_pair": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, ViewParams, _p, _p, _sz, _p]),
     "vipant_wave_view": (_i32, [_p, _i64, _p, _p, _i64, _p, _i64, ViewParams, _p, _p, _sz, _p]),
     "vipant_pcm_wave": (_i32, [_p, _i64, _p, _p, _i32, _i64, _p, _i64, _p, _i64, _p]),
     "vipant_image_view_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),

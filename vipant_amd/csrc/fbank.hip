@@ -24,6 +24,7 @@ struct FbankArgs {
     const float* mix_lambda; const float* mix_mean;                                // vipant_fbank_mix only
     int T, F, size, shift;
     float preemph, norm_mean, norm_std;
+    float* out2; const int32_t* masks2;                                            // vipant_fbank_view_pair only: the second view
 };
 
 __global__ __launch_bounds__(256) void clip_mean_kernel(const float* __restrict__ wave, int64_t stride,
@@ -317,8 +318,15 @@ constexpr int MAXF = 256;         // mel bins
 // MODE_VIEW: the clip's length comes from its plan and the samples from view_sample (the transformed waveform is never stored).
 enum : int { MODE_PLAIN = 0, MODE_MIX = 1, MODE_VIEW = 2 };
 
-template <int NFFT, int MODE>
+// PAIR (MODE_VIEW only): two views of the same clips that differ in their masks alone (a.out / a.masks and a.out2 / a.masks2).  A
+// frame pair whose two frames are live in the same way in both views is transformed once and stored twice.  Where the views
+// disagree (a time-mask edge of one view inside the pair) each view that has a live frame gets a transform of its own, with
+// exactly the frames it has live: a frame that is not live enters the packed transform as zeros, and its partner's rounding
+// depends on that, so this is what keeps each view the bits of the single-view launch.
+template <int NFFT, int MODE, bool PAIR>
 __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
+    static_assert(!PAIR || MODE == MODE_VIEW, "the pair launch is a view launch");
+    constexpr int NV = PAIR ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_off[MAXF + 1], s_start[MAXF], s_len[MAXF];
     const int lane = threadIdx.x & 63;
@@ -365,9 +373,16 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     }
     const int nframes = n < a.size ? 0 : (int)(1 + (n - a.size) / a.shift);
     const float cmean = a.clip_mean != nullptr ? a.clip_mean[clip] : 0.f;
-    const int32_t* mk = a.masks != nullptr ? a.masks + (int64_t)clip * 4 : nullptr;
-    int f0 = 0, f1 = 0, t0 = 0, t1 = 0;
-    if (mk != nullptr) { f0 = mk[0]; f1 = mk[1]; t0 = mk[2]; t1 = mk[3]; }
+    int vf0[NV], vf1[NV], vt0[NV], vt1[NV];
+    float* vout[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int32_t* vm = v == 0 ? a.masks : a.masks2;
+        const int32_t* mk = vm != nullptr ? vm + (int64_t)clip * 4 : nullptr;
+        vf0[v] = vf1[v] = vt0[v] = vt1[v] = 0;
+        if (mk != nullptr) { vf0[v] = mk[0]; vf1[v] = mk[1]; vt0[v] = mk[2]; vt1[v] = mk[3]; }
+        vout[v] = v == 0 ? a.out : a.out2;
+    }
     int partner = -1;
     int64_t np = 0;
     float lam = 1.f, oml = 0.f, pmean = 0.f, xmean = 0.f;
@@ -384,23 +399,45 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     //   X_a[k] = (Z[k] + conj Z[N-k]) / 2,   X_b[k] = (Z[k] - conj Z[N-k]) / (2i)
     // so |X_a|^2 = ((Zr + Zr')^2 + (Zi - Zi')^2) / 4 and |X_b|^2 = ((Zi + Zi')^2 + (Zr' - Zr)^2) / 4 with Z' = Z[N-k].
     // A wave walks FPW frame pairs (2t, 2t + 1); the FFT's LDS traffic per frame halves.
+    // (every decision below is uniform over the wave: ta depends on the wave, not on the lane)
 #pragma unroll 1
-    for (int it = 0; it < FPW; ++it) {
+    for (int step = 0; step < FPW * NV; ++step) {
+        const int it = step / NV, vw = step % NV;                 // vw: the view whose live frames this transform serves
         const int ta = ((blockIdx.x * FPW + it) * 4 + wave) * 2, tb = ta + 1;
         if (ta >= a.T) break;
-        const bool live_a = ta < nframes && !(ta >= t0 && ta < t1);
-        const bool live_b = tb < a.T && tb < nframes && !(tb >= t0 && tb < t1);
         const float padv = a.norm_std != 0.f ? (0.f - a.norm_mean) / a.norm_std : 0.f;
-        float* dst_a = a.out + ((int64_t)clip * a.T + ta) * a.F;
+        bool vla[NV], vlb[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            vla[v] = ta < nframes && !(ta >= vt0[v] && ta < vt1[v]);
+            vlb[v] = tb < a.T && tb < nframes && !(tb >= vt0[v] && tb < vt1[v]);
+        }
+        if (vw == 0) {
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const int f0 = vf0[v], f1 = vf1[v], t0 = vt0[v], t1 = vt1[v];
+                float* ra = vout[v] + ((int64_t)clip * a.T + ta) * a.F;
+                float* rb = ra + a.F;
+                if (!vla[v]) {                                    // padding row or time-masked row: constant
+                    const bool tm = ta >= t0 && ta < t1;
+                    for (int m = lane; m < a.F; m += 64) ra[m] = (tm || (m >= f0 && m < f1)) ? 0.f : padv;
+                }
+                if (!vlb[v] && tb < a.T) {
+                    const bool tm = tb >= t0 && tb < t1;
+                    for (int m = lane; m < a.F; m += 64) rb[m] = (tm || (m >= f0 && m < f1)) ? 0.f : padv;
+                }
+            }
+        }
+        bool both = false;                                        // this transform's rows go to the second view as well
+        if constexpr (PAIR) {
+            const bool same = vla[0] == vla[1] && vlb[0] == vlb[1];
+            if (vw == 1 && same) continue;                        // served by the first view's transform
+            both = vw == 0 && same;
+        }
+        const bool live_a = vla[vw], live_b = vlb[vw];
+        const int f0 = vf0[vw], f1 = vf1[vw];
+        float* dst_a = vout[vw] + ((int64_t)clip * a.T + ta) * a.F;
         float* dst_b = dst_a + a.F;
-        if (!live_a) {                                            // padding row or time-masked row: constant
-            const bool tm = ta >= t0 && ta < t1;
-            for (int m = lane; m < a.F; m += 64) dst_a[m] = (tm || (m >= f0 && m < f1)) ? 0.f : padv;
-        }
-        if (!live_b && tb < a.T) {
-            const bool tm = tb >= t0 && tb < t1;
-            for (int m = lane; m < a.F; m += 64) dst_b[m] = (tm || (m >= f0 && m < f1)) ? 0.f : padv;
-        }
         if (!live_a && !live_b) continue;
         const float* src = a.wave + (int64_t)clip * a.wave_stride + (int64_t)ta * a.shift;
         const float* psrc = a.wave + (int64_t)(partner >= 0 ? partner : clip) * a.wave_stride;
@@ -491,30 +528,38 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
                 eb += (br * br + bi * bi) * wk;
             }
             const bool fm = m >= f0 && m < f1;
+            bool fm2 = false;
+            float* dst2_a = nullptr;
+            if constexpr (PAIR) {
+                fm2 = m >= vf0[1] && m < vf1[1];
+                dst2_a = vout[1] + ((int64_t)clip * a.T + ta) * a.F;
+            }
             if (live_a) {
                 float v = logf(fmaxf(ea, 1.1920928955078125e-07f));
                 if (a.norm_std != 0.f) v = (v - a.norm_mean) / a.norm_std;
                 dst_a[m] = fm ? 0.f : v;
+                if constexpr (PAIR) { if (both) dst2_a[m] = fm2 ? 0.f : v; }
             }
             if (live_b) {
                 float v = logf(fmaxf(eb, 1.1920928955078125e-07f));
                 if (a.norm_std != 0.f) v = (v - a.norm_mean) / a.norm_std;
                 dst_b[m] = fm ? 0.f : v;
+                if constexpr (PAIR) { if (both) dst2_a[a.F + m] = fm2 ? 0.f : v; }
             }
         }
         wave_lds_sync();                                          // the next pair overwrites both buffers
     }
 }
 
-template <int NFFT, int MODE>
+template <int NFFT, int MODE, bool PAIR = false>
 int32_t launch_fbank(const FbankArgs& a, int64_t b, hipStream_t s) {
     static DeviceOnce once;
     const size_t lds = ((size_t)4 * 2 * NFFT + NFFT / 2) * sizeof(float2) + (size_t)2 * NFFT * sizeof(float);
     if (first_on_device(once)) {
-        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)fbank_kernel<NFFT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        VIPANT_HIP_TRY(hipFuncSetAttribute((const void*)fbank_kernel<NFFT, MODE, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         done_on_device(once);
     }
-    hipLaunchKernelGGL((fbank_kernel<NFFT, MODE>), dim3((unsigned)((a.T + 8 * FPW - 1) / (8 * FPW)), (unsigned)b), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((fbank_kernel<NFFT, MODE, PAIR>), dim3((unsigned)((a.T + 8 * FPW - 1) / (8 * FPW)), (unsigned)b), dim3(256), lds, s, a);
     VIPANT_LAUNCH_CHECK();
     return VIPANT_OK;
 }
@@ -613,28 +658,66 @@ int32_t launch_view_plan(const char* who, const float* wave, int64_t wave_stride
 
 }  // namespace
 
-extern "C" int32_t vipant_fbank_view(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, const float* window,
-                                     const float* banks, const int32_t* bank_start, const int32_t* bank_len, const int32_t* masks,
-                                     int64_t b, int64_t T, int64_t F, int32_t window_size, int32_t window_shift, int32_t nfft,
-                                     float preemphasis, float norm_mean, float norm_std, vipant_view_params view, const double* draws,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-    VIPANT_REQUIRE(b > 0 && b < 65536 && T > 0 && F > 0 && F <= 256, VIPANT_EBADSHAPE, "fbank_view: bad batch b=%ld T=%ld F=%ld", (long)b, (long)T, (long)F);
-    VIPANT_REQUIRE(nfft == 512 || nfft == 1024 || nfft == 2048, VIPANT_EBADSHAPE, "fbank_view: padded window %d not in {512, 1024, 2048}", nfft);
+namespace {
+
+// vipant_fbank_view and vipant_fbank_view_pair: `who` names the entry point in messages, pair selects the two-view kernel
+int32_t fbank_view_common(const char* who, bool pair, const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out,
+                          float* out2, const float* window, const float* banks, const int32_t* bank_start, const int32_t* bank_len,
+                          const int32_t* masks, const int32_t* masks2, int64_t b, int64_t T, int64_t F, int32_t window_size,
+                          int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean, float norm_std,
+                          const vipant_view_params& view, const double* draws, void* workspace, size_t workspace_bytes, void* stream) {
+    VIPANT_REQUIRE(b > 0 && b < 65536 && T > 0 && F > 0 && F <= 256, VIPANT_EBADSHAPE, "%s: bad batch b=%ld T=%ld F=%ld", who, (long)b, (long)T, (long)F);
+    VIPANT_REQUIRE(nfft == 512 || nfft == 1024 || nfft == 2048, VIPANT_EBADSHAPE, "%s: padded window %d not in {512, 1024, 2048}", who, nfft);
     VIPANT_REQUIRE(window_size > 1 && window_size <= nfft && window_size > nfft / 2 && window_shift > 0, VIPANT_EBADSHAPE,
-                   "fbank_view: bad window %d / shift %d for padded size %d", window_size, window_shift, nfft);
+                   "%s: bad window %d / shift %d for padded size %d", who, window_size, window_shift, nfft);
     VIPANT_REQUIRE(out != nullptr && window != nullptr && banks != nullptr && bank_start != nullptr && bank_len != nullptr, VIPANT_EBADSHAPE,
-                   "fbank_view: null argument");
+                   "%s: null argument", who);
+    if (pair) {
+        VIPANT_REQUIRE(out2 != nullptr, VIPANT_EBADSHAPE, "%s: null second output", who);
+        const uintptr_t lo = (uintptr_t)out, lo2 = (uintptr_t)out2, bytes = (uintptr_t)(b * T * F) * sizeof(float);
+        VIPANT_REQUIRE(lo + bytes <= lo2 || lo2 + bytes <= lo, VIPANT_EBADSHAPE, "%s: the two outputs overlap", who);
+    }
     hipStream_t s = (hipStream_t)stream;
-    const int32_t rc = launch_view_plan("fbank_view", wave, wave_stride, nsamples, b, view, draws, workspace, workspace_bytes, s);
+    const int32_t rc = launch_view_plan(who, wave, wave_stride, nsamples, b, view, draws, workspace, workspace_bytes, s);
     if (rc != VIPANT_OK) return rc;
     FbankArgs a{wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, nullptr, {nullptr}, nullptr, nullptr,
-                (int)T, (int)F, window_size, window_shift, preemphasis, norm_mean, norm_std};
+                (int)T, (int)F, window_size, window_shift, preemphasis, norm_mean, norm_std, out2, masks2};
     a.plan = (const ViewPlan*)workspace;
+    if (pair) {
+        switch (nfft) {
+            case 512: return launch_fbank<512, MODE_VIEW, true>(a, b, s);
+            case 1024: return launch_fbank<1024, MODE_VIEW, true>(a, b, s);
+            default: return launch_fbank<2048, MODE_VIEW, true>(a, b, s);
+        }
+    }
     switch (nfft) {
         case 512: return launch_fbank<512, MODE_VIEW>(a, b, s);
         case 1024: return launch_fbank<1024, MODE_VIEW>(a, b, s);
         default: return launch_fbank<2048, MODE_VIEW>(a, b, s);
     }
+}
+
+}  // namespace
+
+extern "C" int32_t vipant_fbank_view(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, const float* window,
+                                     const float* banks, const int32_t* bank_start, const int32_t* bank_len, const int32_t* masks,
+                                     int64_t b, int64_t T, int64_t F, int32_t window_size, int32_t window_shift, int32_t nfft,
+                                     float preemphasis, float norm_mean, float norm_std, vipant_view_params view, const double* draws,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    return fbank_view_common("fbank_view", false, wave, wave_stride, nsamples, out, nullptr, window, banks, bank_start, bank_len, masks,
+                             nullptr, b, T, F, window_size, window_shift, nfft, preemphasis, norm_mean, norm_std, view, draws, workspace,
+                             workspace_bytes, stream);
+}
+
+extern "C" int32_t vipant_fbank_view_pair(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, float* out2,
+                                          const float* window, const float* banks, const int32_t* bank_start, const int32_t* bank_len,
+                                          const int32_t* masks, const int32_t* masks2, int64_t b, int64_t T, int64_t F,
+                                          int32_t window_size, int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean,
+                                          float norm_std, vipant_view_params view, const double* draws, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    return fbank_view_common("fbank_view_pair", true, wave, wave_stride, nsamples, out, out2, window, banks, bank_start, bank_len, masks,
+                             masks2, b, T, F, window_size, window_shift, nfft, preemphasis, norm_mean, norm_std, view, draws, workspace,
+                             workspace_bytes, stream);
 }
 
 extern "C" int32_t vipant_wave_view(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* wave_out, int64_t out_stride,

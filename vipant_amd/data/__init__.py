@@ -1,7 +1,8 @@
 """Dataset builders (cvap/data): host-only code that loader workers run.  Nothing in this package imports the HIP binding or touches
 torch.cuda; the decoded bytes it yields become tensors on the device in the trainers' `make_batch`."""
 from .decode import read_frame, read_wav  # noqa: F401
-from .image_audio import (FrameBatch, ImageAudioSrc, PcmBatch, SrcCollator,  # noqa: F401
-                          build_image_audio_dataloader)
+from .image_audio import (FrameBatch, ImageAudioSiameseSrc, ImageAudioSrc, PcmBatch, SecondView,  # noqa: F401
+                          SiameseSrcCollator, SrcCollator, build_image_audio_dataloader)
 
-__all__ = ["read_wav", "read_frame", "FrameBatch", "PcmBatch", "ImageAudioSrc", "SrcCollator", "build_image_audio_dataloader"]
+__all__ = ["read_wav", "read_frame", "FrameBatch", "PcmBatch", "SecondView", "ImageAudioSrc", "ImageAudioSiameseSrc", "SrcCollator",
+           "SiameseSrcCollator", "build_image_audio_dataloader"]

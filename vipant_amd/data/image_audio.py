@@ -1,6 +1,8 @@
 """The image-audio dataset that reads raw files (cvap/data/image_audio.py:90-222 `ImageAudioDatasetSrc`, builder :333-375), in the
 form the device front-ends want: a worker decodes containers only -- WAV to int16, JPEG / PNG to uint8 (decode.py) -- and the batch
 carries the decoded bytes; waveform, log-mel, augmentation and image transform run on the GPU in the trainer's `make_batch`.
+`running.multi_view` selects the siamese form (:224-305 `ImageAudioDatasetSiameseSrc`): the same payload once, six slots, and
+markers where the reference stores second copies.
 
 Host only: nothing here imports the HIP binding, calls torch.cuda or returns a device tensor -- a loader worker must never open the
 GPU.  Index, path, frame-choice and fallback rules are the reference's; the deviations: a clip whose sample
@@ -165,6 +167,67 @@ class ImageAudioSrc(data.Dataset):
         return self.length
 
 
+class ImageAudioSiameseSrc(ImageAudioSrc):
+    """The siamese trainer's dataset (cvap/data/image_audio.py:224-305 `ImageAudioDatasetSiameseSrc`): two views of one frame and two
+    views of one clip.  Both views of a modality are made on the device from ONE decoded payload, so an item holds the decoded
+    frame and the PCM once -- {"frame": uint8 [h, w, 3], "pcm": int16 [n, ch], "name": id} -- and, when a loss pair reads the
+    pre-computed frame embedding (`model.loss.vp or model.loss.ap`, :290), {"embed": fp32 [E]} as well.  A record whose frame is a
+    single name has no embedding file: its embedding is the random vector under the reference's warning.  `cfg` = the whole
+    configuration (`running` and `model.loss`)."""
+
+    def __init__(self, cfg, data_name, train, decode_audio=None, decode_frame=None, seed=0):
+        super().__init__(cfg.running, data_name, train, decode_audio=decode_audio, decode_frame=decode_frame, seed=seed)
+        if self.frame_emb is None:              # image_audio.py:231
+            raise VipantError("running.frame_emb is None: the siamese src dataset expects the directory of the frame embeddings")
+        lcfg = cfg.model.loss
+        self.with_embed = bool(lcfg.get("vp", False) or lcfg.get("ap", False))
+
+    def __getitem__(self, index):
+        g = self._generator(index)
+        name, aclip_file, frame_file, frame_emb_file = self._process_item(index, g)
+        item = {"name": name}
+        if self.with_embed:
+            item["embed"] = self._embed(frame_emb_file, g)
+        item["frame"] = self._frame(frame_file, g)
+        item["pcm"] = self._pcm(aclip_file)
+        return item
+
+
+class SecondView:
+    """The second view slot of a siamese batch: it holds no data of its own, only the index of the slot whose payload it is a view of
+    (the frames and the PCM of a batch cross the worker boundary, and later the bus to the device, once)."""
+
+    def __init__(self, of):
+        self.of = int(of)
+
+    def to(self, device, non_blocking=False):
+        return self
+
+    def pin_memory(self):
+        return self
+
+
+def _collate_frames(items):
+    b = len(items)
+    hw = torch.tensor([[it["frame"].shape[0], it["frame"].shape[1]] for it in items], dtype=torch.int32)
+    frames = torch.zeros((b, int(hw[:, 0].max()), int(hw[:, 1].max()), 3), dtype=torch.uint8)
+    for i, it in enumerate(items):
+        frames[i, :int(hw[i, 0]), :int(hw[i, 1])] = torch.from_numpy(np.ascontiguousarray(it["frame"]))
+    return FrameBatch(frames, hw)
+
+
+def _collate_pcm(items, sample_rate):
+    b = len(items)
+    nframes = torch.tensor([it["pcm"].shape[0] for it in items], dtype=torch.int64)
+    channels = torch.tensor([it["pcm"].shape[1] for it in items], dtype=torch.int32)
+    stride = max(8, -(-int((nframes * channels).max()) // 8) * 8)
+    pcm = torch.zeros((b, stride), dtype=torch.int16)
+    for i, it in enumerate(items):
+        flat = torch.from_numpy(np.ascontiguousarray(it["pcm"]).reshape(-1))
+        pcm[i, :flat.numel()] = flat
+    return PcmBatch(pcm, nframes, channels, sample_rate)
+
+
 class SrcCollator:
     """Items -> the trainers' five-slot tuple (images, audios, text, labels, names): images a FrameBatch (or fp32 [b, E] embeddings),
     audios a PcmBatch, text int64 [b, 1] zeros and labels int64 [b] zeros as the synthetic loader yields them without text.
@@ -178,22 +241,29 @@ class SrcCollator:
         if all("embed" in it for it in items):
             images = torch.from_numpy(np.stack([np.asarray(it["embed"], dtype=np.float32) for it in items]))
         elif all("frame" in it for it in items):
-            hw = torch.tensor([[it["frame"].shape[0], it["frame"].shape[1]] for it in items], dtype=torch.int32)
-            frames = torch.zeros((b, int(hw[:, 0].max()), int(hw[:, 1].max()), 3), dtype=torch.uint8)
-            for i, it in enumerate(items):
-                frames[i, :int(hw[i, 0]), :int(hw[i, 1])] = torch.from_numpy(np.ascontiguousarray(it["frame"]))
-            images = FrameBatch(frames, hw)
+            images = _collate_frames(items)
         else:
             raise VipantError("a batch mixes frames and frame embeddings (records with a single frame name have no embedding file)")
-        nframes = torch.tensor([it["pcm"].shape[0] for it in items], dtype=torch.int64)
-        channels = torch.tensor([it["pcm"].shape[1] for it in items], dtype=torch.int32)
-        stride = max(8, -(-int((nframes * channels).max()) // 8) * 8)
-        pcm = torch.zeros((b, stride), dtype=torch.int16)
-        for i, it in enumerate(items):
-            flat = torch.from_numpy(np.ascontiguousarray(it["pcm"]).reshape(-1))
-            pcm[i, :flat.numel()] = flat
-        audios = PcmBatch(pcm, nframes, channels, self.sample_rate)
+        audios = _collate_pcm(items, self.sample_rate)
         return (images, audios, torch.zeros(b, 1, dtype=torch.int64), torch.zeros(b, dtype=torch.int64),
+                [it["name"] for it in items])
+
+
+class SiameseSrcCollator:
+    """Items of ImageAudioSiameseSrc -> the siamese trainer's six slots (image, image_v1, image_v2, audio_v1, audio_v2, names), as
+    the reference's collator orders them (image_audio.py:317-325): image fp32 [b, E] embeddings, or the reference's [b, 1, 1, 1] ones
+    when no loss pair reads them; image_v1 a FrameBatch and audio_v1 a PcmBatch; image_v2 and audio_v2 SecondView markers of slots
+    1 and 3.  Everything is on the CPU."""
+
+    def __init__(self, sample_rate=16000):
+        self.sample_rate = int(sample_rate)
+
+    def __call__(self, items):
+        if all("embed" in it for it in items):
+            image = torch.from_numpy(np.stack([np.asarray(it["embed"], dtype=np.float32) for it in items]))
+        else:
+            image = torch.ones(len(items), 1, 1, 1)
+        return (image, _collate_frames(items), SecondView(1), _collate_pcm(items, self.sample_rate), SecondView(3),
                 [it["name"] for it in items])
 
 
@@ -207,8 +277,11 @@ def build_image_audio_dataloader(cfg, data_name, shuffle=True, train=True, decod
     if not data_name.startswith("src") or str(rcfg.data_root).startswith("gs://"):
         raise VipantError(f"unrecognized dataset `{data_name}`.")
     if rcfg.get("multi_view", False):
-        raise VipantError("the siamese src dataset: not built")
-    dataset = ImageAudioSrc(rcfg, data_name, train, decode_audio=decode_audio, decode_frame=decode_frame, seed=int(cfg.seed))
+        dataset = ImageAudioSiameseSrc(cfg, data_name, train, decode_audio=decode_audio, decode_frame=decode_frame, seed=int(cfg.seed))
+        collator = SiameseSrcCollator(dataset.sample_rate)
+    else:
+        dataset = ImageAudioSrc(rcfg, data_name, train, decode_audio=decode_audio, decode_frame=decode_frame, seed=int(cfg.seed))
+        collator = SrcCollator(dataset.sample_rate)
     replicas = torch.distributed.is_available() and torch.distributed.is_initialized()
     if replicas:
         sampler = data.distributed.DistributedSampler(dataset, shuffle=shuffle, drop_last=True)
@@ -216,7 +289,7 @@ def build_image_audio_dataloader(cfg, data_name, shuffle=True, train=True, decod
         sampler = data.RandomSampler(dataset) if shuffle else data.SequentialSampler(dataset)
     workers = int(cfg.get("num_proc", 0) or 0)
     loader = data.DataLoader(
-        dataset, batch_size=int(rcfg.batch_size), collate_fn=SrcCollator(dataset.sample_rate), num_workers=workers, pin_memory=True,
+        dataset, batch_size=int(rcfg.batch_size), collate_fn=collator, num_workers=workers, pin_memory=True,
         sampler=sampler, drop_last=bool(replicas),
         # spawn: a forked worker would inherit the parent's open device
         multiprocessing_context=("spawn" if workers > 0 else None))

@@ -14,6 +14,9 @@ always the crop to int((max_len / 100 + 0.05) * sample_rate) samples with its st
 on the host (`draw_views`), one reduction launch turns them into a per-clip plan, and the frame loader forms each sample from
 the original clip: the transformed waveform is never stored (`view_wave` materialises it for whoever wants to look at it).
 
+The siamese dataset wants two SpecAugment views of one log-mel (FbankTransform, transform.py:223-258): `pair=True` writes both from
+one filter-bank launch (`vipant_fbank_view_pair`), each with the bits of the single call under its masks.
+
 The filter tables (Hann window, mel weights) are built once per (sample rate, bins) with torch ops on the device.
 SpecAugment start / width draws follow torchaudio.functional.mask_along_axis (two uniform draws per mask, CPU generator),
 one (frequency, time) pair per clip as the reference's per-item transform does.
@@ -188,14 +191,19 @@ class KaldiFbank:
     def num_frames(self, num_samples: int) -> int:
         return 0 if num_samples < self.size else 1 + (num_samples - self.size) // self.shift
 
-    def draw_masks(self, b: int, generator: Optional[torch.Generator] = None) -> Optional[torch.Tensor]:
-        """[b, 4] int32 (f0, f1, t0, t1); mask_along_axis's draws: value = U*param, min = U*(size - value)."""
-        if self.freq_mask_param <= 0 and self.time_mask_param <= 0:
+    def draw_masks(self, b: int, generator: Optional[torch.Generator] = None, *, freq_mask_param: Optional[int] = None,
+                   time_mask_param: Optional[int] = None) -> Optional[torch.Tensor]:
+        """[b, 4] int32 (f0, f1, t0, t1); mask_along_axis's draws: value = U*param, min = U*(size - value).
+        freq_mask_param / time_mask_param override the object's own for this call (the siamese dataset's FbankTransform draws a
+        prime set (32, 200) and a second set (48, 300) over one log-mel, transform.py:223-258); the generator is consumed alike."""
+        fparam = self.freq_mask_param if freq_mask_param is None else int(freq_mask_param)
+        tparam = self.time_mask_param if time_mask_param is None else int(time_mask_param)
+        if fparam <= 0 and tparam <= 0:
             return None
         rows = []
         for _ in range(b):
             row = []
-            for param, size in ((self.freq_mask_param, self.num_mel_bins), (self.time_mask_param, self.max_len)):
+            for param, size in ((fparam, self.num_mel_bins), (tparam, self.max_len)):
                 if param <= 0:
                     row += [0, 0]
                     continue
@@ -241,6 +249,14 @@ class KaldiFbank:
             lo, hi = float(cfg["snr_min_db"]), float(cfg["snr_max_db"])
             draws[:, 4] = torch.where(u[:, 4] <= float(cfg["p"]), u[:, 5] * (hi - lo + 1.0) + lo, draws[:, 4])
         return draws, seed
+
+    @staticmethod
+    def no_views(b: int):
+        """The view that changes nothing and draws nothing -> (draws, seed): the value `draw_views` leaves where no transform fires,
+        with the pipeline's window at the head (it only matters to a clip longer than `crop_len`)."""
+        draws = torch.zeros(b, 6, dtype=torch.float64)
+        draws[:, 1], draws[:, 4] = 1.0, -1.0
+        return draws, 0
 
     def _view_args(self, view, b: int, n: int, dev):
         """view = (draws, seed) or True -> (ViewParams, draws on the device)."""
@@ -303,14 +319,23 @@ class KaldiFbank:
         return out, nout
 
     def __call__(self, wave: torch.Tensor, nsamples: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None,
-                 mix=None, view=None):
+                 mix=None, view=None, masks2: Optional[torch.Tensor] = None, pair: bool = False):
         """wave fp32 [b, n] on the device (rows zero-padded to a common n), nsamples int64 [b] valid lengths
         (default: n), masks int32 [b, 4] or None  ->  [b, 1, max_len, num_mel_bins] fp32.
         mix = (index int32 [b], lambda fp32 [b]) (draw_mixup): clip i becomes lambda c_i + (1 - lambda) c_index[i] on the
         zero-mean waveforms, inside the launch (vipant_fbank_mix; zero_mean_wf is implied, as in the reference's clf loader).
         view = (draws, seed) (draw_views): the waveform chain of `audio_transforms`, the pipeline's crop with its standard-deviation
         rule and the zero-mean, inside the launch (vipant_fbank_view); view = True: the crop rule only (centred when not training).
-        `view` and `mix` exclude each other, as the reference's `cst` and `clf` loaders do (audioset_cls.py:374-432)."""
+        `view` and `mix` exclude each other, as the reference's `cst` and `clf` loaders do (audioset_cls.py:374-432).
+        pair = True (with a view): two views of the same log-mel that differ in their masks alone, from one filter-bank launch
+        (vipant_fbank_view_pair) -> (out under `masks`, out2 under `masks2`), each [b, 1, max_len, num_mel_bins] with the bits the
+        single call gives for its masks and the same view; either mask set may be None."""
+        if pair and mix is not None:
+            raise VipantError("fbank: `pair` and `mix` exclude each other (the two views of the siamese dataset are never mixed)")
+        if pair and (view is None or view is False):
+            raise VipantError("fbank: `pair` needs a view ((draws, seed), or True for the crop rule only)")
+        if masks2 is not None and not pair:
+            raise VipantError("fbank: `masks2` belongs to the second view of `pair=True`")
         if view is not None and view is not False and mix is not None:
             raise VipantError("fbank: `view` and `mix` exclude each other (the reference's clf loader mixes, its cst loader transforms)")
         wave, nsamples = self._wave_args(wave, nsamples)
@@ -332,6 +357,18 @@ class KaldiFbank:
                  self.num_mel_bins, self.size, self.shift, self.padded, self.preemphasis, float(mean), float(std), ws.data_ptr(),
                  ws.numel(), ops._stream())
             return out
+        if pair:
+            if masks2 is not None:
+                masks2 = masks2.to(device=dev, dtype=torch.int32).contiguous()
+            out2 = torch.empty_like(out)
+            params, draws = self._view_args(view, b, n, dev)
+            ws = ops.scratch("fbank", query("vipant_fbank_view_workspace_bytes", b), dev)
+            call("vipant_fbank_view_pair", wave.data_ptr(), n, nsamples.data_ptr(), out.data_ptr(), out2.data_ptr(),
+                 self.window.data_ptr(), self.banks.data_ptr(), self.bank_start.data_ptr(), self.bank_len.data_ptr(),
+                 masks.data_ptr() if masks is not None else None, masks2.data_ptr() if masks2 is not None else None, b,
+                 self.max_len, self.num_mel_bins, self.size, self.shift, self.padded, self.preemphasis, float(mean), float(std),
+                 params, draws.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
+            return out, out2
         if view is not None and view is not False:
             params, draws = self._view_args(view, b, n, dev)
             ws = ops.scratch("fbank", query("vipant_fbank_view_workspace_bytes", b), dev)

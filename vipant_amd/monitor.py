@@ -11,8 +11,9 @@ Deliberate deviations (documented in DESIGN.md):
   * with `running.data_root` empty (the default) batches come from a synthetic loader with the reference's tensor contract,
     unless a loader is injected through `dataloader=`.  With `running.data_root=DIR` the bimodal VA trainer reads the reference's
     raw-file image-audio dataset (vipant_amd/data, cvap/data/image_audio.py:90-222): loader workers decode containers only, and
-    `make_batch` runs waveform, log-mel, augmentation and image transform on the device; the reference's
-    other dataset builders are not built.
+    `make_batch` runs waveform, log-mel, augmentation and image transform on the device; under
+    `running.multi_view` the siamese trainer reads the siamese form of that dataset (cvap/data/image_audio.py:224-305; section 18);
+    the reference's other dataset builders are not built.
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ import torch
 
 from . import parallel
 from ._ffi import VipantError
-from .data import FrameBatch, PcmBatch
+from .data import FrameBatch, PcmBatch, SecondView
 from .model import build_main_model
 from .module import LARS, adjust_learning_rate, exclude_bias_or_norm
 
@@ -563,10 +564,64 @@ class VASMonitor(Monitor):
     epoch loop is the base trainer's; what differs is the batch -- five slots, of which only the views that a live pair of
     `model.loss` reads are moved to the device, image views rescaled bilinearly to `running.resolution` -- and the worker's
     signature.  View slots that hold uint8 frames (`running.image_frames`) become the prime and the second `barlow` view of
-    vipant_amd/image_views.py instead (`clip` under `running.clip_tf` and at evaluation); the second only when `model.loss.vv`."""
+    vipant_amd/image_views.py instead (`clip` under `running.clip_tf` and at evaluation); the second only when `model.loss.vv`.
+    With `running.data_root` the batch comes from the siamese raw-file dataset (vipant_amd/data: frames and PCM once, `SecondView`
+    markers in the second view slots) and both audio views from one log-mel launch (`audio_views_from_pcm`)."""
     with_text = False
+    # FbankTransform's own normalisation (cvap/data/audio/transform.py:228-229, :238-239, :247-248): the siamese dataset does not
+    # read `running.audio.norms`
+    FBANK_NORMS = (-4.93839311, 5.75751113)
+    PRIME_MASKS = (32, 200)         # transform_prime: FrequencyMasking(32), TimeMasking(200) -> view 1
+    SECOND_MASKS = (48, 300)        # transform: FrequencyMasking(48), TimeMasking(300) -> view 2
+
+    def eval_norms(self):
+        raise VipantError("running.audio.eval_norms under running.multi_view: the siamese dataset normalises with FbankTransform's "
+                          "own constants and has no statistics run (take them with monitor=VAMonitor)")
+
+    def siamese_frontend(self, train, sample_rate):
+        from .frontend import KaldiFbank
+        cache = self.__dict__.setdefault("_siamese_fbank", {})
+        key = (bool(train), int(sample_rate))
+        if key not in cache:
+            acfg = self.cfg.running.audio
+            cache[key] = KaldiFbank(float(sample_rate), acfg.num_mel_bins, acfg.max_len, self.FBANK_NORMS, acfg.get("zero_mean_wf", True),
+                                    acfg.get("frame_shift", 10), device=self.device, train=train)
+        return cache[key]
+
+    def audio_views_from_pcm(self, clips):
+        """A PcmBatch -> (view 1, view 2 or None), log-mels [b, 1, T, F] on the device, as the siamese dataset makes them
+        (cvap/data/image_audio.py:256-285, transform.py:223-258): H2D, the waveform (`pcm_wave`, channel 0, no tiling), then ONE
+        log-mel launch that writes both views (`vipant_fbank_view_pair`).  No waveform chain whatever `running.audio.transform_audio`
+        says (:238); the pipeline's crop of a clip longer than `crop_len`, drawn when training and centred at evaluation;
+        `zero_mean_wf` from the config; FbankTransform's constants, not `running.audio.norms`.  Training masks view 1 with the prime
+        set (32, 200) and view 2 with the second set (48, 300); view 2 exists only under `model.loss.aa` (otherwise the single
+        `vipant_fbank_view` launch).  Evaluation: view 1 unmasked, no view 2.
+        Draws per training step, from the per-rank generator `_aug_generator()` in this order: `draw_views(b)` if a clip of the
+        batch is longer than `crop_len`; `draw_masks(b, freq_mask_param=32, time_mask_param=200)`; under `model.loss.aa`
+        `draw_masks(b, freq_mask_param=48, time_mask_param=300)`.  Evaluation draws nothing."""
+        from .frontend import pcm_wave
+        train, both = self._training(), bool(self.cfg.model.loss.aa)
+        fbank = self.siamese_frontend(train, clips.sample_rate)
+        n = torch.minimum(clips.nframes, clips.pcm.shape[1] // clips.channels.clamp(1, 8).long()).clamp_(min=0)      # (no device sync)
+        longest = int(n.max())
+        on_dev = clips.to(self.device, non_blocking=True)
+        wave, nsamples = pcm_wave(on_dev.pcm, on_dev.nframes, on_dev.channels, mode="first", wave_stride=max(8, -(-longest // 8) * 8))
+        b = wave.shape[0]
+        if not train:
+            return fbank(wave, nsamples, view=True), None
+        if "aug_generator" not in self.__dict__:
+            self.aug_generator = self._aug_generator()
+        view = fbank.draw_views(b, self.aug_generator) if longest > fbank.crop_len else fbank.no_views(b)
+        masks = fbank.draw_masks(b, self.aug_generator, freq_mask_param=self.PRIME_MASKS[0], time_mask_param=self.PRIME_MASKS[1])
+        if not both:
+            return fbank(wave, nsamples, masks=masks, view=view), None
+        masks2 = fbank.draw_masks(b, self.aug_generator, freq_mask_param=self.SECOND_MASKS[0], time_mask_param=self.SECOND_MASKS[1])
+        return fbank(wave, nsamples, masks=masks, view=view, masks2=masks2, pair=True)
 
     def make_batch(self, batch):
+        """The six slots of a siamese batch -> tensors on the device.  A file batch (`running.data_root`) holds a FrameBatch and a
+        PcmBatch in the first view slots and SecondView markers in the second: one upload of the frames serves both image views,
+        one upload of the PCM both audio views (`audio_views_from_pcm`)."""
         lcfg, res = self.cfg.model.loss, self.cfg.running.resolution
 
         def to_dev(x):
@@ -577,10 +632,24 @@ class VASMonitor(Monitor):
                 images = torch.nn.functional.interpolate(images, res, mode="bilinear", align_corners=False)
             return images
         images = to_dev(batch[0]) if lcfg.vp or lcfg.ap else None
-        images_v1 = scale_images(self.image_views(to_dev(batch[1]), "prime", siamese=True))
-        images_v2 = scale_images(self.image_views(to_dev(batch[2]), "second", siamese=True)) if lcfg.vv else None
-        audios_v1 = to_dev(batch[3]).unsqueeze(1)
-        audios_v2 = to_dev(batch[4]).unsqueeze(1) if lcfg.aa else None
+        if isinstance(batch[1], FrameBatch):
+            second = batch[batch[2].of] if isinstance(batch[2], SecondView) else batch[2]
+            if second is not batch[1]:
+                raise VipantError("a siamese file batch: the second image view must be a view of the first slot's frames")
+            frames, hw = batch[1].frames.to(self.device, non_blocking=True), batch[1].hw
+            images_v1 = scale_images(self.image_views(frames, "prime", siamese=True, hw=hw))
+            images_v2 = scale_images(self.image_views(frames, "second", siamese=True, hw=hw)) if lcfg.vv else None
+        else:
+            images_v1 = scale_images(self.image_views(to_dev(batch[1]), "prime", siamese=True))
+            images_v2 = scale_images(self.image_views(to_dev(batch[2]), "second", siamese=True)) if lcfg.vv else None
+        if isinstance(batch[3], PcmBatch):
+            second = batch[batch[4].of] if isinstance(batch[4], SecondView) else batch[4]
+            if second is not batch[3]:
+                raise VipantError("a siamese file batch: the second audio view must be a view of the first slot's clips")
+            audios_v1, audios_v2 = self.audio_views_from_pcm(batch[3])
+        else:
+            audios_v1 = to_dev(batch[3]).unsqueeze(1)
+            audios_v2 = to_dev(batch[4]).unsqueeze(1) if lcfg.aa else None
         return images, images_v1, images_v2, audios_v1, audios_v2, batch[-1]
 
     def _step_inputs(self, batch):
