@@ -24,6 +24,9 @@ _running_common = {
     "train_samples": 1.0, "test_samples": 5000,
     # the rate every clip of a `data_root` dataset must have (vipant_amd/data: one batched filter-bank launch has one rate)
     "sample_rate": 16000,
+    # the CLIP vocabulary file the caption datasets tokenise with (vipant_amd/tokenizer.py); "": bpe_simple_vocab_16e6.txt.gz inside
+    # `clip_model_root`, then inside `data_root`
+    "bpe_path": "",
     # dataset-free operation (this build): synthetic spectrogram / token batches, SURVEY.md 8-D2
     "synthetic": True, "synthetic_steps": 8, "precomputed_image": False,
     # activation-memory plan for batches that do not fit: towers in micro-batches under one global-batch loss,

@@ -104,12 +104,15 @@ class ImageAudioSrc(data.Dataset):
         """The item's own generator: the training draws of item `index` in epoch `epoch` (evaluation draws nothing that varies)."""
         return torch.Generator().manual_seed(self.seed + 13 + int(index) + 1000003 * (self.epoch if self.train else 0))
 
-    def _process_item(self, index, generator=None):
-        """image_audio.py:131-151 -> (name, clip file, frame file, frame embedding file or None)."""
+    def _process_item(self, index, generator=None, frames=True):
+        """image_audio.py:131-151 -> (name, clip file, frame file, frame embedding file or None).  `frames=False` (a dataset that
+        shows no image: audio_text.py): the clip alone, the record's frames are not read and nothing is drawn."""
         record = self.dataset[index]
         name, sub = record["id"], record.get("dir", "")
         base = f"{self.data_root}/{sub}/" if sub else f"{self.data_root}/"            # a record without `dir` reads from the root
         clip_file = f"{base}{self.aclip_key}/{name}.{record[self.aclip_key][0]}"        # the first extension listed
+        if not frames:
+            return name, clip_file, None, None
         frame, embed_file = record[self.frame_key], None
         if not isinstance(frame, str):                                                 # a list of frame names: pick one
             if self.train:

@@ -13,7 +13,8 @@ Deliberate deviations (documented in DESIGN.md):
     raw-file image-audio dataset (vipant_amd/data, cvap/data/image_audio.py:90-222): loader workers decode containers only, and
     `make_batch` runs waveform, log-mel, augmentation and image transform on the device; under
     `running.multi_view` the siamese trainer reads the siamese form of that dataset (cvap/data/image_audio.py:224-305; section 18);
-    the reference's other dataset builders are not built.
+    the AT trainer reads the caption datasets (`data_name=audiocaps*` / `clotho*`: cvap/data/audiocaps.py, audio_text.py; section
+    19), without the AudioSet label map; the reference's other dataset builders are not built.
 """
 from __future__ import annotations
 
@@ -193,11 +194,12 @@ class Monitor(object):
 
     # ------------------------------------------------------------------ cvap.py:67-87
     def build_file_data(self):
-        """`running.data_root=DIR`: the raw-file image-audio dataset, and when training the evaluation loader if its index exists."""
+        """`running.data_root=DIR`: the raw-file image-audio dataset, and when training the evaluation loader if its index exists
+        (a trainer with text: the caption datasets, `build_caption_data`)."""
         from .data import build_image_audio_dataloader
         rcfg = self.cfg.running
         if self.with_text:
-            raise VipantError("running.data_root: the audio-text dataset is not built (the image-audio dataset serves monitor=VAMonitor)")
+            return self.build_caption_data()
         data_name = rcfg.eval_name if self.cfg.eval else rcfg.data_name
         _, loader = build_image_audio_dataloader(self.cfg, data_name, shuffle=(not self.cfg.eval), train=(not self.cfg.eval))
         nstep = len(loader)
@@ -210,6 +212,39 @@ class Monitor(object):
             _, self.evalloader = build_image_audio_dataloader(self.cfg, eval_name, shuffle=False, train=False)
             self.echo(f"Will do evaluation every {rcfg.save_rate} steps on {len(self.evalloader)} batches.")
             self.gold_file = f"{rcfg.data_root}/{eval_name}.csv"
+        return loader
+
+    # ------------------------------------------------------------------ cvalp.py:65-104
+    def build_caption_data(self):
+        """`running.data_root=DIR` under a trainer with text: the caption datasets (vipant_amd/data/audio_text.py; `audiocaps*`,
+        `clotho*`), and when training the evaluation and the test loader whose index exists.  No label map: the reference builds one
+        from AudioSet ontology files that the caption datasets never read."""
+        from .data import build_audio_text_dataloader
+        rcfg = self.cfg.running
+        data_name = str(rcfg.eval_name if self.cfg.eval else rcfg.data_name)
+        if data_name.startswith(("src", "npz")):
+            raise VipantError(f"running.data_name=`{data_name}` under monitor=VALMonitor: the AudioSet datasets with text are not built; "
+                              "the data names that work here begin with `audiocaps` or `clotho`")
+        _, loader = build_audio_text_dataloader(self.cfg, data_name, shuffle=(not self.cfg.eval), train=(not self.cfg.eval))
+        nstep = len(loader)
+        if nstep < rcfg.peep_rate:
+            rcfg.peep_rate = nstep
+        self.echo(f"Instantiate main dataloader from `{data_name}': total {nstep} batches.")
+        self.gold_file = f"{rcfg.data_root}/{data_name}.csv"
+
+        def side_loader(name):
+            name = "" if self.cfg.eval else str(name or "")
+            if not name or not os.path.isfile(f"{rcfg.data_root}/{name}.csv"):
+                return None
+            return build_audio_text_dataloader(self.cfg, name, shuffle=False, train=False)[1]
+        self.evalloader = side_loader(rcfg.eval_name)
+        if self.evalloader is not None:
+            self.echo(f"Will do evaluation every {rcfg.save_rate} steps on {len(self.evalloader)} batches ({rcfg.eval_name}).")
+            self.gold_file = f"{rcfg.data_root}/{rcfg.eval_name}.csv"
+        self.testloader = side_loader(rcfg.test_name)
+        if self.testloader is not None:
+            self.echo(f"Will do test every {rcfg.save_rate} steps on {len(self.testloader)} batches ({rcfg.test_name}).")
+            self.gold_file_test = f"{rcfg.data_root}/{rcfg.test_name}.csv"
         return loader
 
     # ------------------------------------------------------------------ cvap.py:43-65
