@@ -388,6 +388,21 @@ int32_t vipant_fbank_mix(const float* wave, int64_t wave_stride, const int64_t* 
                          const int32_t* mix_index, const float* mix_lambda, int64_t b, int64_t T, int64_t F,
                          int32_t window_size, int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean,
                          float norm_std, void* workspace, size_t workspace_bytes, void* stream);
+/* vipant_fbank_mix whose partners may lie OUTSIDE the batch (the reference draws a clip's partner from the whole dataset in the loader
+ * worker, audioset_cls.py:374-400; a file loader hands the device b clips plus up to b partner clips).  wave fp32 [nsrc, wave_stride]
+ * and nsamples int64 [nsrc] with nsrc >= b; out fp32 [b, T, F] is made from rows 0 .. b-1 only: rows b .. nsrc-1 are read as
+ * partners and produce no output (a row nobody points at is never read past its mean).  mix_index int32 [b] takes values in
+ * [-1, nsrc); the kernel clamps what the host cannot see (below -1: not mixed; nsrc and above: row nsrc - 1).  The mix rule, the
+ * fixed-order reductions and everything after them are vipant_fbank_mix's: with nsrc == b the two entry points give the same bits,
+ * and for any partner layout the result equals rows 0 .. b-1 of vipant_fbank_mix over all nsrc rows with mix_index -1 for rows >= b.
+ * Workspace: vipant_fbank_mix_src_workspace_bytes(nsrc, b) (nsrc clip means and b mixed means).  Refused before any launch, nothing
+ * written: a NULL argument (masks excepted), b < 1, nsrc < b, wave_stride < 1, a bad T / F / nfft / window. */
+size_t vipant_fbank_mix_src_workspace_bytes(int64_t nsrc, int64_t b);
+int32_t vipant_fbank_mix_src(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, const float* window,
+                             const float* banks, const int32_t* bank_start, const int32_t* bank_len, const int32_t* masks,
+                             const int32_t* mix_index, const float* mix_lambda, int64_t nsrc, int64_t b, int64_t T, int64_t F,
+                             int32_t window_size, int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean,
+                             float norm_std, void* workspace, size_t workspace_bytes, void* stream);
 /* vipant_fbank on a VIEW of every clip: the reference's waveform transforms and its crop rule (cvap/data/audio/transform.py:75-202
  * and :24-28) inside the launch.  A clip passes, in this order, through
  *   flip     s1[i] = s0[n0-1-i] when its flip draw is >= 0.5;
@@ -584,6 +599,18 @@ int32_t vipant_bce_logits(const float* z, int64_t ldz, const uint8_t* targets, i
 int32_t vipant_bce_logits_soft(const float* z, int64_t ldz, const float* targets, int64_t ldt, const float* logit_scale, float* loss,
                                uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp, int64_t row0, int64_t nrows,
                                float grad_scale, int64_t B, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+/* Tagging targets from ragged class-id lists (the reference builds multi-hot rows of 527 as Python lists per item in the loader worker
+ * and mixes them there, audioset_cls.py:400).  ids int32 [total]; offsets int32 [nsrc + 1]: row r's classes are
+ * ids[offsets[r] : offsets[r+1]]; mix_index int32 [b] / mix_lambda fp32 [b] as in vipant_fbank_mix_src, or both NULL; y fp32 [b, C]:
+ *   y[i, c] = lam_i [c in L_i] + (1 - lam_i) [c in L_p],  p = mix_index[i]
+ * in fp32 with 1 - lam, each product and the sum rounded separately (the bits of lam * y + (1 - lam) * y[partner] on dense rows).
+ * Without mix arguments, or with p < 0, y[i, c] is exactly [c in L_i].  Every element of y is written once by the one thread that
+ * owns it (no memset-then-scatter: a duplicate id gives 1).  An id outside [0, C) is ignored; offsets are clamped so that nothing
+ * outside ids[0 : total] is read (a decreasing pair is an empty list); mix_index is clamped like vipant_fbank_mix_src's.  One launch,
+ * no workspace, no allocation, no synchronisation.  Refused, nothing written: NULL ids / offsets / y, total < 0, b < 1, nsrc < b,
+ * C < 1, exactly one of the two mix pointers NULL. */
+int32_t vipant_multihot_mix(const int32_t* ids, int64_t total, const int32_t* offsets, const int32_t* mix_index,
+                            const float* mix_lambda, float* y, int64_t nsrc, int64_t b, int64_t C, void* stream);
 
 /* ==== The fused operator set: one entry point per reference operator group, forward and backward ==========
  * Host-side compositions of the kernels above (vipant_amd/csrc/block.hip): same stream, no allocation, no synchronisation.

@@ -120,6 +120,9 @@ PROTOTYPES = {
     "vipant_fbank": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _f32, _f32, _p, _sz, _p]),
     "vipant_fbank_mix_workspace_bytes": (_sz, [_i64]),
     "vipant_fbank_mix": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _p, _sz, _p]),
+    "vipant_fbank_mix_src_workspace_bytes": (_sz, [_i64, _i64]),
+    "vipant_fbank_mix_src": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _p, _sz, _p]),
+    "vipant_multihot_mix": (_i32, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "vipant_fbank_view_workspace_bytes": (_sz, [_i64]),
     "vipant_fbank_view": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, ViewParams, _p, _p, _sz, _p]),
     "vipant_fbank_view_pair": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _f32, ViewParams, _p, _p, _sz, _p]),

@@ -9,6 +9,9 @@
 // butterflies over the 64 lanes; the sums over rows are two-level and fixed-order: the four waves of a workgroup add their rows
 // through LDS in wave order into part[workgroup], one workgroup then sums the partials in index order in fp64.  No float
 // atomics: two runs are bit-identical.
+//
+// vipant_multihot_mix forms the tagging targets those heads score from ragged class-id lists (and mixup's soft targets from a
+// clip's list and its partner's): one launch, every element written once by the thread that owns it.
 #include "common.h"
 
 #define CLS_WAVES 4     // rows per workgroup
@@ -209,7 +212,55 @@ __global__ __launch_bounds__(256) void cls_finish(const float* __restrict__ part
     }
 }
 
+// ---- tagging targets from ragged class-id lists --------------------------------------------------------------------------
+// One workgroup row per output row (blockIdx.x), 256 classes per workgroup and pass; every thread owns its elements y[i, c] and
+// decides them by walking the clip's list and its partner's (a handful of ids each, the same addresses for the whole wave), so
+// each element is written once whatever the lists hold: duplicates give 1, ids outside [0, C) match no c.  The products and the
+// sum are rounded one by one (__fmul_rn / __fadd_rn: no contraction to FMA) -- the bits of `lam * y + (1 - lam) * y[p]` in torch.
+__global__ __launch_bounds__(256) void multihot_mix_kernel(const int32_t* __restrict__ ids, int total, const int32_t* __restrict__ offsets,
+                                                           const int32_t* __restrict__ mix_index, const float* __restrict__ mix_lambda,
+                                                           float* __restrict__ y, int nsrc, int C) {
+    const int row = blockIdx.x;
+    auto bounds = [&](int r, int& lo, int& hi) {                  // clamped: nothing outside ids[0 : total] is read
+        lo = offsets[r]; hi = offsets[r + 1];
+        lo = lo < 0 ? 0 : (lo > total ? total : lo);
+        hi = hi < lo ? lo : (hi > total ? total : hi);
+    };
+    int lo, hi, plo = 0, phi = 0;
+    bounds(row, lo, hi);
+    int p = -1;
+    float lam = 1.f, oml = 0.f;
+    if (mix_index != nullptr) {
+        p = mix_index[row];
+        p = p < 0 ? -1 : (p >= nsrc ? nsrc - 1 : p);
+        if (p >= 0) {
+            bounds(p, plo, phi);
+            lam = mix_lambda[row];
+            oml = __fsub_rn(1.0f, lam);
+        }
+    }
+    for (int c = blockIdx.y * 256 + threadIdx.x; c < C; c += gridDim.y * 256) {
+        float own = 0.f, par = 0.f;
+        for (int k = lo; k < hi; ++k) own = ids[k] == c ? 1.f : own;
+        for (int k = plo; k < phi; ++k) par = ids[k] == c ? 1.f : par;
+        y[(int64_t)row * C + c] = p >= 0 ? __fadd_rn(__fmul_rn(lam, own), __fmul_rn(oml, par)) : own;
+    }
+}
+
 // ---- host entry points ------------------------------------------------------------------------------------------------
+extern "C" int32_t vipant_multihot_mix(const int32_t* ids, int64_t total, const int32_t* offsets, const int32_t* mix_index,
+                                       const float* mix_lambda, float* y, int64_t nsrc, int64_t b, int64_t C, void* stream) {
+    VIPANT_REQUIRE(ids != nullptr && offsets != nullptr && y != nullptr, VIPANT_EBADSHAPE, "multihot_mix: ids, offsets and y are required");
+    VIPANT_REQUIRE(b > 0 && nsrc >= b && C > 0 && total >= 0 && nsrc < (1ll << 31) - 1 && C < (1ll << 30) && total < (1ll << 31),
+                   VIPANT_EBADSHAPE, "multihot_mix: bad shape b=%ld nsrc=%ld C=%ld total=%ld", (long)b, (long)nsrc, (long)C, (long)total);
+    VIPANT_REQUIRE((mix_index == nullptr) == (mix_lambda == nullptr), VIPANT_EBADSHAPE, "multihot_mix: mix_index and mix_lambda go together");
+    const int64_t chunks = ceil_div(C, 256);
+    hipLaunchKernelGGL(multihot_mix_kernel, dim3((unsigned)b, (unsigned)(chunks < 1024 ? chunks : 1024)), dim3(256), 0, (hipStream_t)stream,
+                       ids, (int)total, offsets, mix_index, mix_lambda, y, (int)nsrc, (int)C);
+    VIPANT_LAUNCH_CHECK();
+    return VIPANT_OK;
+}
+
 extern "C" size_t vipant_softmax_ce_workspace_bytes(int64_t nrows) { return (size_t)(cls_groups(nrows) * 2 * sizeof(float)); }
 extern "C" size_t vipant_bce_logits_workspace_bytes(int64_t nrows) { return (size_t)(cls_groups(nrows) * 2 * sizeof(float)); }
 

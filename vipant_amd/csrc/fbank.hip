@@ -25,6 +25,7 @@ struct FbankArgs {
     int T, F, size, shift;
     float preemph, norm_mean, norm_std;
     float* out2; const int32_t* masks2;                                            // vipant_fbank_view_pair only: the second view
+    int nsrc;                                                                      // vipant_fbank_mix(_src) only: rows of wave (>= the grid's b)
 };
 
 __global__ __launch_bounds__(256) void clip_mean_kernel(const float* __restrict__ wave, int64_t stride,
@@ -44,10 +45,11 @@ __global__ __launch_bounds__(256) void clip_mean_kernel(const float* __restrict_
     if (threadIdx.x == 0) mean[clip] = n > 0 ? red[0] / (float)n : 0.f;
 }
 
-// the partner of a clip: mix_index clamped into [-1, b) -- the host cannot see a device array's values
-__device__ __forceinline__ int mix_partner(const int32_t* __restrict__ mix_index, int clip, int b) {
+// the partner of a clip: mix_index clamped into [-1, nsrc) -- the host cannot see a device array's values.  nsrc is the number of
+// rows of wave, passed explicitly: the partner rows of vipant_fbank_mix_src lie past the b rows the grid covers.
+__device__ __forceinline__ int mix_partner(const int32_t* __restrict__ mix_index, int clip, int nsrc) {
     const int p = mix_index[clip];
-    return p < 0 ? -1 : (p >= b ? b - 1 : p);
+    return p < 0 ? -1 : (p >= nsrc ? nsrc - 1 : p);
 }
 
 // mixup on the waveform (cvap/data/audioset_cls.py:374-398): mean over nsamples[i] of x = lam c_i + (1 - lam) c_p, c = w - mean(w),
@@ -60,11 +62,12 @@ __global__ __launch_bounds__(MIX_MEAN_THREADS) void mix_mean_kernel(const float*
                                                                     const int64_t* __restrict__ nsamples,
                                                                     const int32_t* __restrict__ mix_index,
                                                                     const float* __restrict__ mix_lambda,
-                                                                    const float* __restrict__ mean, float* __restrict__ mix_mean) {
+                                                                    const float* __restrict__ mean, float* __restrict__ mix_mean,
+                                                                    int nsrc) {
     constexpr int NT = MIX_MEAN_THREADS;
     __shared__ float red[NT];
     const int clip = blockIdx.x;
-    const int p = mix_partner(mix_index, clip, (int)gridDim.x);
+    const int p = mix_partner(mix_index, clip, nsrc);
     if (p < 0) {                                                  // uniform over the workgroup
         if (threadIdx.x == 0) mix_mean[clip] = 0.f;
         return;
@@ -387,7 +390,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     int64_t np = 0;
     float lam = 1.f, oml = 0.f, pmean = 0.f, xmean = 0.f;
     if constexpr (MODE == MODE_MIX) {
-        partner = mix_partner(a.mix_index, clip, (int)gridDim.y);
+        partner = mix_partner(a.mix_index, clip, a.nsrc);
         if (partner >= 0) {
             np = a.nsamples[partner] < a.wave_stride ? a.nsamples[partner] : a.wave_stride;
             lam = a.mix_lambda[clip]; oml = 1.f - lam;
@@ -597,6 +600,42 @@ extern "C" int32_t vipant_fbank(const float* wave, int64_t wave_stride, const in
     }
 }
 
+namespace {
+
+// vipant_fbank_mix is the nsrc == b case: the same three launches with the same grids over the b output rows, so it keeps its bits
+int32_t fbank_mix_impl(const char* who, const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, const float* window,
+                       const float* banks, const int32_t* bank_start, const int32_t* bank_len, const int32_t* masks,
+                       const int32_t* mix_index, const float* mix_lambda, int64_t nsrc, int64_t b, int64_t T, int64_t F,
+                       int32_t window_size, int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean, float norm_std,
+                       void* workspace, size_t workspace_bytes, size_t workspace_need, void* stream) {
+    VIPANT_REQUIRE(b > 0 && b < 65536 && T > 0 && F > 0 && F <= 256, VIPANT_EBADSHAPE, "%s: bad batch b=%ld T=%ld F=%ld", who, (long)b, (long)T, (long)F);
+    VIPANT_REQUIRE(nsrc >= b && nsrc < 65536, VIPANT_EBADSHAPE, "%s: %ld source rows for b=%ld", who, (long)nsrc, (long)b);
+    VIPANT_REQUIRE(nfft == 512 || nfft == 1024 || nfft == 2048, VIPANT_EBADSHAPE, "%s: padded window %d not in {512, 1024, 2048}", who, nfft);
+    VIPANT_REQUIRE(window_size > 1 && window_size <= nfft && window_size > nfft / 2 && window_shift > 0, VIPANT_EBADSHAPE,
+                   "%s: bad window %d / shift %d for padded size %d", who, window_size, window_shift, nfft);
+    VIPANT_REQUIRE(wave != nullptr && nsamples != nullptr && out != nullptr && window != nullptr && banks != nullptr &&
+                       bank_start != nullptr && bank_len != nullptr && mix_index != nullptr && mix_lambda != nullptr,
+                   VIPANT_EBADSHAPE, "%s: null argument", who);
+    VIPANT_REQUIRE(workspace != nullptr && workspace_bytes >= workspace_need, VIPANT_ENOWORKSPACE, "%s: workspace too small", who);
+    hipStream_t s = (hipStream_t)stream;
+    float* cmean = (float*)workspace;                             // nsrc means, then the b means of the mixed clips
+    float* xmean = cmean + nsrc;
+    hipLaunchKernelGGL(clip_mean_kernel, dim3((unsigned)nsrc), dim3(256), 0, s, wave, wave_stride, nsamples, cmean);
+    VIPANT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mix_mean_kernel, dim3((unsigned)b), dim3(MIX_MEAN_THREADS), 0, s, wave, wave_stride, nsamples, mix_index, mix_lambda, cmean, xmean,
+                       (int)nsrc);
+    VIPANT_LAUNCH_CHECK();
+    FbankArgs a{wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, cmean, mix_index, mix_lambda, xmean,
+                (int)T, (int)F, window_size, window_shift, preemphasis, norm_mean, norm_std, nullptr, nullptr, (int)nsrc};
+    switch (nfft) {
+        case 512: return launch_fbank<512, MODE_MIX>(a, b, s);
+        case 1024: return launch_fbank<1024, MODE_MIX>(a, b, s);
+        default: return launch_fbank<2048, MODE_MIX>(a, b, s);
+    }
+}
+
+}  // namespace
+
 // per-clip means only: mean(w_i) and the mean of the mixed clip, b floats each
 extern "C" size_t vipant_fbank_mix_workspace_bytes(int64_t b) { return (size_t)((b * 8 + 255) / 256 * 256); }
 
@@ -605,29 +644,23 @@ extern "C" int32_t vipant_fbank_mix(const float* wave, int64_t wave_stride, cons
                                     const int32_t* mix_index, const float* mix_lambda, int64_t b, int64_t T, int64_t F,
                                     int32_t window_size, int32_t window_shift, int32_t nfft, float preemphasis, float norm_mean,
                                     float norm_std, void* workspace, size_t workspace_bytes, void* stream) {
-    VIPANT_REQUIRE(b > 0 && b < 65536 && T > 0 && F > 0 && F <= 256, VIPANT_EBADSHAPE, "fbank_mix: bad batch b=%ld T=%ld F=%ld", (long)b, (long)T, (long)F);
-    VIPANT_REQUIRE(nfft == 512 || nfft == 1024 || nfft == 2048, VIPANT_EBADSHAPE, "fbank_mix: padded window %d not in {512, 1024, 2048}", nfft);
-    VIPANT_REQUIRE(window_size > 1 && window_size <= nfft && window_size > nfft / 2 && window_shift > 0, VIPANT_EBADSHAPE,
-                   "fbank_mix: bad window %d / shift %d for padded size %d", window_size, window_shift, nfft);
-    VIPANT_REQUIRE(wave != nullptr && nsamples != nullptr && out != nullptr && window != nullptr && banks != nullptr &&
-                       bank_start != nullptr && bank_len != nullptr && mix_index != nullptr && mix_lambda != nullptr,
-                   VIPANT_EBADSHAPE, "fbank_mix: null argument");
-    VIPANT_REQUIRE(workspace != nullptr && workspace_bytes >= vipant_fbank_mix_workspace_bytes(b), VIPANT_ENOWORKSPACE,
-                   "fbank_mix: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    float* cmean = (float*)workspace;
-    float* xmean = cmean + b;
-    hipLaunchKernelGGL(clip_mean_kernel, dim3((unsigned)b), dim3(256), 0, s, wave, wave_stride, nsamples, cmean);
-    VIPANT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mix_mean_kernel, dim3((unsigned)b), dim3(MIX_MEAN_THREADS), 0, s, wave, wave_stride, nsamples, mix_index, mix_lambda, cmean, xmean);
-    VIPANT_LAUNCH_CHECK();
-    FbankArgs a{wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, cmean, mix_index, mix_lambda, xmean,
-                (int)T, (int)F, window_size, window_shift, preemphasis, norm_mean, norm_std};
-    switch (nfft) {
-        case 512: return launch_fbank<512, MODE_MIX>(a, b, s);
-        case 1024: return launch_fbank<1024, MODE_MIX>(a, b, s);
-        default: return launch_fbank<2048, MODE_MIX>(a, b, s);
-    }
+    return fbank_mix_impl("fbank_mix", wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, mix_index, mix_lambda,
+                          b, b, T, F, window_size, window_shift, nfft, preemphasis, norm_mean, norm_std, workspace, workspace_bytes,
+                          b > 0 ? vipant_fbank_mix_workspace_bytes(b) : 0, stream);
+}
+
+// mean(w_r) of all nsrc rows and the mean of the b mixed clips
+extern "C" size_t vipant_fbank_mix_src_workspace_bytes(int64_t nsrc, int64_t b) { return (size_t)(((nsrc + b) * 4 + 255) / 256 * 256); }
+
+extern "C" int32_t vipant_fbank_mix_src(const float* wave, int64_t wave_stride, const int64_t* nsamples, float* out, const float* window,
+                                        const float* banks, const int32_t* bank_start, const int32_t* bank_len, const int32_t* masks,
+                                        const int32_t* mix_index, const float* mix_lambda, int64_t nsrc, int64_t b, int64_t T,
+                                        int64_t F, int32_t window_size, int32_t window_shift, int32_t nfft, float preemphasis,
+                                        float norm_mean, float norm_std, void* workspace, size_t workspace_bytes, void* stream) {
+    VIPANT_REQUIRE(wave_stride >= 1, VIPANT_EBADSHAPE, "fbank_mix_src: bad stride %ld", (long)wave_stride);
+    return fbank_mix_impl("fbank_mix_src", wave, wave_stride, nsamples, out, window, banks, bank_start, bank_len, masks, mix_index,
+                          mix_lambda, nsrc, b, T, F, window_size, window_shift, nfft, preemphasis, norm_mean, norm_std, workspace,
+                          workspace_bytes, b > 0 && nsrc >= b ? vipant_fbank_mix_src_workspace_bytes(nsrc, b) : 0, stream);
 }
 
 // one 64-byte plan per clip

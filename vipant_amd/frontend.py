@@ -4,7 +4,8 @@ The reference computes one Kaldi filter bank per clip on CPU dataloader workers
 (cvap/data/audio/transform.py:12-35, parameters cvap/data/image_audio.py:119-126), pads / normalises it and applies
 SpecAugment masks (image_audio.py:183-207, configs/running/audio/default.yaml).  `KaldiFbank` does the same for a whole
 batch of device-resident waveforms in two launches (`vipant_fbank`; three with waveform mixup, `vipant_fbank_mix`) and returns the [b, 1, T, F] tensor
-`ViTPreEncoder` takes.  File decoding stays with the loader (vipant_amd/data); `pcm_wave` turns the 16-bit PCM it decodes into
+`ViTPreEncoder` takes.  With `outputs=b` the mixup partners may be rows of `wave` past the b clips of the batch (`vipant_fbank_mix_src`):
+the file loader draws a partner from the whole dataset and ships its clip behind the batch; such a row is read, never written.  File decoding stays with the loader (vipant_amd/data); `pcm_wave` turns the 16-bit PCM it decodes into
 those waveforms in one launch (`vipant_pcm_wave`: int16 -> fp32, the channel rule, `tile_audio`).  There is no resampling.
 
 What the reference does to the waveform in front of the filter bank (transform.py:22-28) happens inside the launch as well
@@ -319,11 +320,14 @@ class KaldiFbank:
         return out, nout
 
     def __call__(self, wave: torch.Tensor, nsamples: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None,
-                 mix=None, view=None, masks2: Optional[torch.Tensor] = None, pair: bool = False):
+                 mix=None, view=None, masks2: Optional[torch.Tensor] = None, pair: bool = False, outputs: Optional[int] = None):
         """wave fp32 [b, n] on the device (rows zero-padded to a common n), nsamples int64 [b] valid lengths
         (default: n), masks int32 [b, 4] or None  ->  [b, 1, max_len, num_mel_bins] fp32.
         mix = (index int32 [b], lambda fp32 [b]) (draw_mixup): clip i becomes lambda c_i + (1 - lambda) c_index[i] on the
         zero-mean waveforms, inside the launch (vipant_fbank_mix; zero_mean_wf is implied, as in the reference's clf loader).
+        outputs = b' (with mix): only rows 0 .. b'-1 of wave produce a log-mel; the rows past them are mixup partners from outside the
+        batch, which index may point at (values in [-1, rows of wave)); index / lambda / masks have b' rows and the result is
+        [b', 1, max_len, num_mel_bins] (vipant_fbank_mix_src when wave has more rows than b').
         view = (draws, seed) (draw_views): the waveform chain of `audio_transforms`, the pipeline's crop with its standard-deviation
         rule and the zero-mean, inside the launch (vipant_fbank_view); view = True: the crop rule only (centred when not training).
         `view` and `mix` exclude each other, as the reference's `cst` and `clf` loaders do (audioset_cls.py:374-432).
@@ -341,8 +345,17 @@ class KaldiFbank:
         wave, nsamples = self._wave_args(wave, nsamples)
         b, n = wave.shape
         dev = wave.device
+        nsrc = b
+        if outputs is not None:
+            if mix is None:
+                raise VipantError("fbank: `outputs` belongs to `mix` (the rows past it are mixup partners)")
+            if not 1 <= int(outputs) <= nsrc:
+                raise VipantError(f"fbank: outputs={outputs} outside [1, {nsrc}] (the rows of wave)")
+            b = int(outputs)
         if masks is not None:
             masks = masks.to(device=dev, dtype=torch.int32).contiguous()
+            if outputs is not None and masks.shape != (b, 4):
+                raise VipantError(f"fbank: masks must have shape [{b}, 4] (one row per output), got {tuple(masks.shape)}")
         out = torch.empty((b, 1, self.max_len, self.num_mel_bins), dtype=F32, device=dev)
         mean, std = self.norms if self.norms else (0.0, 0.0)
         if mix is not None:
@@ -350,6 +363,16 @@ class KaldiFbank:
             lam = mix[1].to(device=dev, dtype=F32).contiguous()
             if index.shape != (b,) or lam.shape != (b,):
                 raise VipantError(f"fbank: mix index / lambda must have shape [{b}], got {tuple(index.shape)} / {tuple(lam.shape)}")
+            if nsrc > b:                                            # partner rows past the batch: they are read, never written
+                if nsamples.shape != (nsrc,):
+                    raise VipantError(f"fbank: nsamples must have shape [{nsrc}], got {tuple(nsamples.shape)}")
+                ws = ops.scratch("fbank", query("vipant_fbank_mix_src_workspace_bytes", nsrc, b), dev)
+                call("vipant_fbank_mix_src", wave.data_ptr(), n, nsamples.data_ptr(), out.data_ptr(), self.window.data_ptr(),
+                     self.banks.data_ptr(), self.bank_start.data_ptr(), self.bank_len.data_ptr(),
+                     masks.data_ptr() if masks is not None else None, index.data_ptr(), lam.data_ptr(), nsrc, b, self.max_len,
+                     self.num_mel_bins, self.size, self.shift, self.padded, self.preemphasis, float(mean), float(std),
+                     ws.data_ptr(), ws.numel(), ops._stream())
+                return out
             ws = ops.scratch("fbank", query("vipant_fbank_mix_workspace_bytes", b), dev)
             call("vipant_fbank_mix", wave.data_ptr(), n, nsamples.data_ptr(), out.data_ptr(), self.window.data_ptr(),
                  self.banks.data_ptr(), self.bank_start.data_ptr(), self.bank_len.data_ptr(),

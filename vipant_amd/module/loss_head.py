@@ -627,12 +627,13 @@ class BCELossHead(_ClassifierHead):
     def zero_shot(self, text, gold_file):
         audios = ops.l2_normalize(torch.cat(self.audios).contiguous())
         text = ops.l2_normalize(text.detach().float().contiguous())
+        nclass = text.shape[0]
+        if nclass % 4:      # the similarity contraction needs a multiple of 4 prompts (AudioSet has 527): zero rows, their columns dropped
+            text = torch.cat([text, text.new_zeros((4 - nclass % 4, text.shape[1]))]).contiguous()
         x1s = torch.empty((audios.shape[0], text.shape[0]), dtype=torch.float32, device=audios.device)
         a16, t16 = ops.cast_bf16(audios)[0], ops.cast_bf16(text)[0]
-        if text.shape[0] % 4:
-            raise VipantError(f"BCELossHead.zero_shot: {text.shape[0]} prompts; the similarity contraction needs a multiple of 4")
         ops.gemm_nt(a16, t16, x1s, epi=ops.EPI_F32)
-        return self.report(gold_file=gold_file, text=None, x1s=x1s.cpu().numpy())
+        return self.report(gold_file=gold_file, text=None, x1s=x1s[:, :nclass].contiguous().cpu().numpy())
 
     def report(self, gold_file=None, x1s=None, x2s=None, **kwargs):
         from ..util.metrics import multilabel_report

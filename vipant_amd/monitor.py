@@ -14,7 +14,9 @@ Deliberate deviations (documented in DESIGN.md):
     `make_batch` runs waveform, log-mel, augmentation and image transform on the device; under
     `running.multi_view` the siamese trainer reads the siamese form of that dataset (cvap/data/image_audio.py:224-305; section 18);
     the AT trainer reads the caption datasets (`data_name=audiocaps*` / `clotho*`: cvap/data/audiocaps.py, audio_text.py; section
-    19), without the AudioSet label map; the reference's other dataset builders are not built.
+    19), without the AudioSet label map; the x-fold trainer reads ESC-50 / UrbanSound8K and the tagging trainer the AudioSet clf
+    dataset with its label map, filter set and dataset-wide mixup partners (cvap/data/esc50.py, audioset_cls.py, audioset_hub.py;
+    section 20); the reference's other dataset builders are not built.
 """
 from __future__ import annotations
 
@@ -324,17 +326,19 @@ class Monitor(object):
             cache[key] = KaldiFbank.from_config(self.cfg.running.audio, float(sample_rate), train=train, device=self.device)
         return cache[key]
 
-    def audios_from_pcm(self, clips):
+    def audios_from_pcm(self, clips, tile=None):
         """A PcmBatch (decoded 16-bit clips, on the host) -> log-mels [b, 1, T, F] on the device, in the reference's order
         (image_audio.py:183-207, transform.py:15-35): H2D, the waveform (`pcm_wave`: channel rule, `tile_audio`), then inside the
         log-mel launch the `audio_transforms` chain and the crop rule, the filter bank, `norms`, and the SpecAugment masks.  Training
         draws views when there is a chain or a clip longer than `crop_len`, and masks under `transform_fbank`; evaluation takes the
-        centred crop of a longer clip and nothing else; `eval_norms` switches chain, masks and norms off."""
+        centred crop of a longer clip and nothing else; `eval_norms` switches chain, masks and norms off.  `tile`: None follows
+        `running.audio.tile_audio`; False never tiles (the x-fold datasets pass `tile_audio=False` whatever the key says, esc50.py:81)."""
         from .frontend import pcm_wave
         acfg = self.cfg.running.audio
         train = self._training()
         fbank = self.pcm_frontend(train, clips.sample_rate)
-        tile_len = int(fbank.max_len / 100 * clips.sample_rate) if acfg.get("tile_audio", False) else 0
+        tile = bool(acfg.get("tile_audio", False)) if tile is None else bool(tile)
+        tile_len = int(fbank.max_len / 100 * clips.sample_rate) if tile else 0
         # the lengths pcm_wave will report, from the host's copy (no device sync)
         n = torch.minimum(clips.nframes, clips.pcm.shape[1] // clips.channels.clamp(1, 8).long()).clamp_(min=0)
         if tile_len > 0:
@@ -797,6 +801,11 @@ class ESCMonitor(Monitor):
         if loader_list is not None:
             self.loader_list, self.lid2str, self.lid2int, self.label_map = loader_list
             return len(self.lid2str)
+        if self._from_files():                                    # esc50_clf.py:41-49: ESC-50 / UrbanSound8K from `running.data_root`
+            from .data import build_xfold_dataloader_list
+            self.loader_list, self.lid2str, self.lid2int, self.label_map = build_xfold_dataloader_list(self.cfg, echo=self.echo)
+            self.echo(f"Instantiate {len(self.loader_list)}-fold dataloaders from `{rcfg.data_name}': {len(self.lid2str)} classes.")
+            return len(self.lid2str)
         shard = (parallel.rank(), parallel.world_size()) if parallel.active() else (0, 1)
         data = SyntheticFolds(self.cfg, rcfg.get("synthetic_folds", 2), rcfg.get("synthetic_classes", 50),
                               int(rcfg.get("synthetic_steps", 8)) * int(rcfg.batch_size), shard)
@@ -858,7 +867,10 @@ class ESCMonitor(Monitor):
 
     # ------------------------------------------------------------------ esc50_clf.py:122-132
     def make_batch(self, batch):
-        audios = torch.as_tensor(batch[0]).to(self.device, non_blocking=True).unsqueeze(1)
+        if isinstance(batch[0], PcmBatch):                          # decoded clips of a file dataset: never tiled (esc50.py:81)
+            audios = self.audios_from_pcm(batch[0], tile=False)
+        else:
+            audios = torch.as_tensor(batch[0]).to(self.device, non_blocking=True).unsqueeze(1)
         labels = torch.as_tensor(batch[1]).to(self.device, non_blocking=True)
         return audios, labels, batch[2]
 
@@ -1018,8 +1030,12 @@ class ASMonitor(Monitor):
     `monitor=ASMonitor worker=ASClassifier +running=audioset +model/loss=bce`).  The epoch loop, schedules, peep line, periodic
     eval and checkpoint are the base trainer's.  What differs is the batch: waveform batches go through the GPU front-end
     (vipant_amd/frontend.py) inside `make_batch`, and when training with `running.mixup_rate > 0` the clips are mixed in the
-    front-end's launch with partners from the same batch (the reference draws the partner from the dataset in a loader worker)
-    and the labels become lam y + (1 - lam) y[partner], which BCELossHead scores as fractions (`soft_targets`).  Without mixup
+    front-end's launch and the labels become lam y + (1 - lam) y[partner], which BCELossHead scores as fractions
+    (`soft_targets`).  With `running.data_root=DIR` the batches come from the raw-file tagging dataset (vipant_amd/data/classify.py):
+    as in the reference a loader worker draws a clip's partner from the whole DATASET, the partner clips ride behind the batch,
+    the launch reads them as rows that produce no output (`KaldiFbank(mix=, outputs=)`, vipant_fbank_mix_src) and the soft
+    targets are formed on the device from the ragged class lists (vipant_multihot_mix).  Synthetic batches (`data_root` empty)
+    keep the in-batch rule: the trainer draws the partner among the clips of the batch (`draw_mixup`).  Without mixup
     (`running.clf=False`, or `mixup_rate` 0) the batch takes the reference's other branch: the `running.audio.audio_transforms`
     chain when `transform_audio` is on and the model is training, and the crop rule for clips longer than the front-end's
     `crop_len`, both inside the front-end's launch (`KaldiFbank.draw_views`, `view=`).
@@ -1049,6 +1065,8 @@ class ASMonitor(Monitor):
 
     def build_data(self, dataloader=None):
         rcfg = self.cfg.running
+        if dataloader is None and self._from_files():
+            return self.build_file_data()
         steps, rank = int(rcfg.get("synthetic_steps", 8)), max(int(self.cfg.rank), 0)
         evalloader = SyntheticTagging(self.cfg, steps, False, 0)
         self.lid2int = evalloader.lid2int
@@ -1060,6 +1078,44 @@ class ASMonitor(Monitor):
         self.echo(f"Instantiate main dataloader from `synthetic': total {len(self.dataloader)} batches, "
                   f"{evalloader.nclass} sound classes.")
         return evalloader.nclass
+
+    # ------------------------------------------------------------------ audioset_clf.py:100-145
+    def build_file_data(self):
+        """`running.data_root=DIR`: label map and filter set, the main loader (`eval_name` when evaluating) and, when training, the
+        evaluation and test loaders whose index exists; `lid2int` = the label map's prompts, one ragged token row per class."""
+        from .data import build_audioset_clf_dataloader, build_audioset_label_map, build_filter_set
+        rcfg = self.cfg.running
+        label_map = build_audioset_label_map(rcfg.data_root, label_map=rcfg.label_map, prompt=str(rcfg.get("prompt", "") or ""), rcfg=rcfg)
+        lid2int = [0] * len(label_map)
+        for k, v in label_map.items():
+            lid2int[v[0]] = v[2]
+        self.lid2int = lid2int
+        filters = build_filter_set(rcfg.data_root, rcfg.get("filter_set", None))
+        if filters is not None:
+            self.echo(f"At most {len(filters)} audio clips for training becuase of filtering.")
+        self.echo(f"Total {len(label_map)} sound classes.")
+        data_name = rcfg.eval_name if self.cfg.eval else rcfg.data_name
+        _, self.dataloader = build_audioset_clf_dataloader(
+            self.cfg, data_name, label_map, shuffle=(not self.cfg.eval and not rcfg.audio.get("eval_norms", False)),
+            train=(not self.cfg.eval), filters=filters, echo=self.echo)
+        self.echo(f"Instantiate main dataloader from `{data_name}': total {len(self.dataloader)} batches.")
+        self.gold_file = f"{rcfg.data_root}/{data_name}.csv"
+
+        def side_loader(name):
+            name = "IGNORE_ME" if self.cfg.eval else str(name or "IGNORE_ME")
+            path = f"{rcfg.data_root}/{name}"
+            if not (os.path.isdir(path) or os.path.isfile(f"{path}.csv")):
+                return None
+            return build_audioset_clf_dataloader(self.cfg, name, label_map, shuffle=False, train=False, echo=self.echo)[1]
+        self.evalloader = side_loader(rcfg.eval_name)
+        if self.evalloader is not None:
+            self.echo(f"Will do evaluation every {rcfg.save_rate} steps on {len(self.evalloader)} batches ({rcfg.eval_name}).")
+            self.gold_file = f"{rcfg.data_root}/{rcfg.eval_name}.csv"
+        self.testloader = side_loader(rcfg.test_name)
+        if self.testloader is not None:
+            self.echo(f"Will do test every {rcfg.save_rate} steps on {len(self.testloader)} batches ({rcfg.test_name}).")
+            self.gold_file_test = f"{rcfg.data_root}/{rcfg.test_name}.csv"
+        return len(label_map)
 
     def frontend(self, train):
         from .frontend import KaldiFbank
@@ -1077,8 +1133,36 @@ class ASMonitor(Monitor):
         partner = torch.where(index < 0, torch.arange(y.shape[0], device=y.device), index)
         return lam * y + (1.0 - lam) * y[partner]
 
+    def make_tagging_batch(self, batch):
+        """A batch of the raw-file tagging dataset (TaggingCollator): b clips and, behind them, the p partner clips the workers drew
+        (audioset_cls.py:374-400).  H2D and the waveform of all b + p rows (`pcm_wave`: channel 0, never tiled -- `wf[:1]`), masks
+        for the b outputs, then one log-mel launch that mixes on the way into LDS and writes b rows, and one launch that forms
+        the (soft) multi-hot targets from the ragged class lists.  The waveform is always zero-mean (:377), a longer clip is cut at
+        `max_len` frames (:410).  At evaluation there are no partners and no masks, and the targets are exact {0, 1}."""
+        from . import ops
+        from .frontend import pcm_wave
+        clips, tags = batch[1], batch[3]
+        images = self.image_views(torch.as_tensor(batch[0]).to(self.device, non_blocking=True))
+        train = self.model.training
+        fbank = self.pcm_frontend(train, clips.sample_rate)
+        b = int(tags.mix_index.shape[0])
+        n = torch.minimum(clips.nframes, clips.pcm.shape[1] // clips.channels.clamp(1, 8).long()).clamp_(min=0)
+        on_dev = clips.to(self.device, non_blocking=True)
+        wave, nsamples = pcm_wave(on_dev.pcm, on_dev.nframes, on_dev.channels, mode="first", tile_len=0,
+                                  wave_stride=max(8, -(-int(n.max()) // 8) * 8))
+        masks = fbank.draw_masks(b, self.aug_generator) if train else None
+        tags = tags.to(self.device, non_blocking=True)
+        mix = (tags.mix_index, tags.mix_lambda)
+        audios = fbank(wave, nsamples, masks=masks, mix=mix, outputs=b)
+        labels = ops.multihot_mix(tags.ids, tags.offsets, tags.num_label, outputs=b, mix=mix)
+        if not self.model.loss_head.soft_targets:
+            labels = labels.long()                                  # multi-hot marks, the dtype the synthetic loader yields
+        return images, audios, None, labels, batch[-1]
+
     # ------------------------------------------------------------------ audioset_clf.py:192-210
     def make_batch(self, batch):
+        if isinstance(batch[1], PcmBatch):
+            return self.make_tagging_batch(batch)
         images = self.image_views(torch.as_tensor(batch[0]).to(self.device, non_blocking=True))
         audios = torch.as_tensor(batch[1]).to(self.device, non_blocking=True)
         labels = torch.as_tensor(batch[3]).to(self.device, non_blocking=True)
@@ -1141,7 +1225,10 @@ class ASMonitor(Monitor):
         return self.model.report(gold_file=gold_file, **report_kwargs)
 
     def zero_shot(self, dataloader, samples=float("inf"), iepoch=0, gold_file=None):
-        text = torch.cat([self.model.encode_text(torch.tensor(self.lid2int[s:s + 50], device=self.device))
+        def padded(rows):                                           # audioset_clf.py:366-367: zip_longest(fillvalue=0) per chunk
+            width = max(len(row) for row in rows)
+            return [list(row) + [0] * (width - len(row)) for row in rows]
+        text = torch.cat([self.model.encode_text(torch.tensor(padded(self.lid2int[s:s + 50]), device=self.device))
                           for s in range(0, len(self.lid2int), 50)])
         return self.infer(dataloader, samples=samples, iepoch=iepoch, gold_file=gold_file, text=text)
 

@@ -1521,6 +1521,32 @@ def _bce(entry, z, targets, logit_scale, C, row0, nrows, grad_scale, want_grad, 
     return loss, dz, dscale, prob
 
 
+def multihot_mix(ids: torch.Tensor, offsets: torch.Tensor, C: int, *, outputs: Optional[int] = None, mix=None) -> torch.Tensor:
+    """Ragged class-id lists -> (soft) multi-hot targets fp32 [b, C] (vipant_multihot_mix).  ids int32 [total], offsets int32
+    [nsrc + 1] (row r's classes are ids[offsets[r] : offsets[r + 1]]), b = outputs (default nsrc); mix = (index int32 [b] with values
+    in [-1, nsrc), lambda fp32 [b]) or None: y[i] = lam_i [L_i] + (1 - lam_i) [L_index[i]], the bits of ASMonitor.soft_labels on the
+    dense rows; without mix, or where index is -1, exactly the {0, 1} row."""
+    _need(ids, torch.int32, "multihot_mix.ids"); _need(offsets, torch.int32, "multihot_mix.offsets")
+    if ids.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise _ffi.VipantError(f"multihot_mix: ids [total] and offsets [nsrc + 1] expected, got {tuple(ids.shape)} / {tuple(offsets.shape)}")
+    nsrc = offsets.numel() - 1
+    b = nsrc if outputs is None else int(outputs)
+    dev = ids.device
+    total = ids.numel()
+    if total == 0:                                                  # every list empty: the entry point still wants a pointer
+        ids = torch.zeros((1,), dtype=torch.int32, device=dev)
+    index = lam = None
+    if mix is not None:
+        index = mix[0].to(device=dev, dtype=torch.int32).contiguous()
+        lam = mix[1].to(device=dev, dtype=F32).contiguous()
+        if index.shape != (b,) or lam.shape != (b,):
+            raise _ffi.VipantError(f"multihot_mix: mix index / lambda must have shape [{b}], got {tuple(index.shape)} / {tuple(lam.shape)}")
+    y = torch.empty((max(b, 0), int(C)), dtype=F32, device=dev)
+    call("vipant_multihot_mix", ids.data_ptr(), total, offsets.data_ptr(), _ptr(index), _ptr(lam), y.data_ptr(), nsrc, b, int(C),
+         _stream())
+    return y
+
+
 _padded: Dict[tuple, tuple] = {}
 
 
