@@ -93,7 +93,10 @@ int32_t vipant_colsum_bf16(const uint16_t* X, int64_t ldx, float* out, int64_t M
  * residual stream).
  * q / qscale (optional, both or neither; here and in vipant_layernorm_bwd): the block quantisation of the bf16 output fused into the
  * pass (the row is in registers anyway): q bytes [M, D] / qscale bytes [vipant_mx_scale_bytes(M, D)] = vipant_quant_e4m3_mx of y
- * resp. dx_bf16, bit for bit. */
+ * resp. dx_bf16, bit for bit.
+ * Widths (here and in vipant_layernorm_bwd): D = 64 H, 3 <= H <= 16 (192 .. 1024).  The multiples of 256 run one wave per row; the
+ * others run lane groups of 16 / 32 / 64 lanes per row (csrc/layernorm_widths.hip) and have no e4m3 output.  Refused with
+ * VIPANT_EBADSHAPE before any launch, nothing written: M <= 0, any other D, q / qscale at a D that is no multiple of 256. */
 int32_t vipant_layernorm_fwd(const void* x, int64_t ldx, const float* gamma, const float* beta, uint16_t* y, float* y_f32,
                              float* mean, float* rstd, int64_t M, int64_t D, const uint16_t* add, void* sum_out, uint8_t* q,
                              uint8_t* qscale, int32_t stream_flags, void* stream);
@@ -864,7 +867,7 @@ int32_t vipant_ln_mlp_quickgelu_bwd(const uint16_t* dy, const uint16_t* w_proj_t
  * (mean_channels ? 1 : Cw)*ph*pw, P = nrow*ncol, S = P+1); out fp32 [b*S,Dw] = the residual stream; mean / rstd fp32 [b*S].
  * Refused with VIPANT_EBADSHAPE before the first launch, nothing written: b, C, Dw, Cw, ph, pw, sh or sw <= 0; T < ph or F < pw;
  * pw % 8 != 0; kcols % 64 != 0; C != (mean_channels ? 1 : Cw) (the channel-mean kernel has one channel: val.py:245-247 fails in
- * F.conv2d for any other input); Dw not a multiple of 256 up to 1024 (vipant_layernorm_fwd). */
+ * F.conv2d for any other input); Dw not a multiple of 64 from 192 to 1024 (vipant_layernorm_fwd). */
 int32_t vipant_patch_embed_ln_fwd(const float* x, const float* conv_w, const float* cls, const float* pos, const float* gamma,
                                   const float* beta, uint16_t* w_eff, uint16_t* patches, float* tokens, float* out,
                                   float* mean, float* rstd, int64_t b, int64_t C, int64_t T, int64_t F, int64_t Dw, int64_t Cw,
@@ -886,7 +889,7 @@ int32_t vipant_patch_embed_ln_bwd(const void* dout, int32_t dout_bf16, const flo
  * end-of-text rows) the rows are gathered into `rows` fp32 [batch,D]; normalized != 0: out = feat / |feat|, norm fp32 [batch] (else out is unused).
  * With idx == NULL only rows item * S of x are read, forward and backward.  Refused with VIPANT_EBADSHAPE before the first launch,
  * nothing written: batch, S or E <= 0, E % 4 != 0 (the backward: E % 64 != 0 -- its dy = dfeat . proj^T contracts over E), D not a
- * multiple of 256 up to 1024, idx != NULL without `rows` (the backward: without `rows` and `drows`). */
+ * multiple of 64 from 192 to 1024, idx != NULL without `rows` (the backward: without `rows` and `drows`). */
 int32_t vipant_cls_ln_proj_l2norm_fwd(const float* x, const int64_t* idx, const float* gamma, const float* beta,
                                       const uint16_t* proj_t, float* rows, uint16_t* y, float* mean, float* rstd, float* feat,
                                       float* out, float* norm, int64_t batch, int64_t S, int64_t D, int64_t E, int32_t normalized,

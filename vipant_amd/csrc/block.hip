@@ -277,7 +277,7 @@ extern "C" int32_t vipant_patch_embed_ln_fwd(const float* x, const float* conv_w
     const int64_t kcols = (mean_channels ? 1 : Cw) * ph * pw;
     VIPANT_REQUIRE(kcols % 64 == 0, VIPANT_EBADSHAPE, "patch_embed_ln_fwd: (mean_channels ? 1 : Cw) * ph * pw must be a multiple of 64 (%ld)",
                    (long)kcols);
-    VIPANT_REQUIRE(Dw % 256 == 0 && Dw <= 1024, VIPANT_EBADSHAPE, "patch_embed_ln_fwd: the width must be a multiple of 256 up to 1024 (Dw=%ld)",
+    VIPANT_REQUIRE(ln_width_ok(Dw), VIPANT_EBADSHAPE, "patch_embed_ln_fwd: the width must be a multiple of 64 from 192 to 1024 (Dw=%ld)",
                    (long)Dw);
     TRY(vipant_conv_weight_prep(conv_w, w_eff, Dw, Cw, ph * pw, mean_channels, stream));
     TRY(vipant_im2col(x, patches, b, C, T, F, ph, pw, sh, sw, stream));
@@ -319,8 +319,8 @@ extern "C" int32_t vipant_cls_ln_proj_l2norm_fwd(const float* x, const int64_t* 
     const float* src = x;
     int64_t ld = S * D;                       // cls row of every sample: strided view, no copy
     // (the stages' own shape rules, asked here so that a refused call has launched nothing)
-    VIPANT_REQUIRE(batch > 0 && S > 0 && E > 0 && E % 4 == 0 && D > 0 && D % 256 == 0 && D <= 1024, VIPANT_EBADSHAPE,
-                   "cls_ln_proj_l2norm_fwd: need E %% 4 == 0 and D a multiple of 256 up to 1024 (batch=%ld S=%ld D=%ld E=%ld)", (long)batch,
+    VIPANT_REQUIRE(batch > 0 && S > 0 && E > 0 && E % 4 == 0 && ln_width_ok(D), VIPANT_EBADSHAPE,
+                   "cls_ln_proj_l2norm_fwd: need E %% 4 == 0 and D a multiple of 64 from 192 to 1024 (batch=%ld S=%ld D=%ld E=%ld)", (long)batch,
                    (long)S, (long)D, (long)E);
     VIPANT_REQUIRE(idx == nullptr || rows != nullptr, VIPANT_EBADSHAPE, "cls_ln_proj_l2norm_fwd: gathered read-out needs `rows`");
     if (idx != nullptr) {
@@ -348,8 +348,8 @@ extern "C" int32_t vipant_cls_ln_proj_l2norm_bwd(const float* dout, const float*
                    "cls_ln_proj_l2norm_bwd: workspace too small");
     // refused before the first launch, so that a refused call writes nothing: dy = dfeat . proj^T contracts over E (vipant_gemm_nt:
     // K % 64 == 0), and the gathered read-out's LayerNorm backward runs on `rows` into `drows`
-    VIPANT_REQUIRE(batch > 0 && S > 0 && E > 0 && E % 64 == 0 && D % 256 == 0 && D > 0 && D <= 1024, VIPANT_EBADSHAPE,
-                   "cls_ln_proj_l2norm_bwd: need E %% 64 == 0 and D a multiple of 256 up to 1024 (batch=%ld S=%ld D=%ld E=%ld)", (long)batch,
+    VIPANT_REQUIRE(batch > 0 && S > 0 && E > 0 && E % 64 == 0 && ln_width_ok(D), VIPANT_EBADSHAPE,
+                   "cls_ln_proj_l2norm_bwd: need E %% 64 == 0 and D a multiple of 64 from 192 to 1024 (batch=%ld S=%ld D=%ld E=%ld)", (long)batch,
                    (long)S, (long)D, (long)E);
     VIPANT_REQUIRE(idx == nullptr || (rows != nullptr && drows != nullptr), VIPANT_EBADSHAPE,
                    "cls_ln_proj_l2norm_bwd: the gathered read-out needs `rows` and `drows`");

@@ -51,6 +51,20 @@ void vipant_set_error(const char* fmt, ...);
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- the widths vipant_layernorm_fwd / _bwd take ------------------------------------------------
+// A transformer tower's width: 64 H with 3 <= H <= 16.  The multiples of 256 run the kernels of layernorm.hip (the only ones with an
+// e4m3 output), the others those of layernorm_widths.hip.  Callers that launch something before their LayerNorm ask this first.
+static inline bool ln_width_ok(int64_t D) { return D % 64 == 0 && D >= 192 && D <= 1024; }
+static inline bool ln_width_has_e4m3(int64_t D) { return D % 256 == 0 && D >= 256 && D <= 1024; }
+// layernorm_widths.hip: the launchers for ln_width_ok(D) && !ln_width_has_e4m3(D); arguments as the kernels of layernorm.hip take them
+__attribute__((visibility("hidden"))) int32_t ln_widths_fwd(const void* x, int64_t ldx, const float* gamma, const float* beta, bf16_t* y,
+                                                            float* y32, float* mean, float* rstd, int64_t M, int64_t D, const bf16_t* add,
+                                                            void* sum_out, bool in16, bool out16, hipStream_t s);
+__attribute__((visibility("hidden"))) int32_t ln_widths_bwd(const void* dy, bool dy_is_f32, bool dres_bf16, bool x16, const void* x,
+                                                            int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                                                            const void* dres, float* dx, int64_t lddx, bf16_t* dxb, float* partial,
+                                                            int blocks, int64_t M, int64_t D, hipStream_t s);
+
 // One-time set-up of a launcher (the dynamic-LDS opt-in of its kernels, hipFuncSetAttribute) is a property of the DEVICE, not of the
 // process: bit d of the launcher's mask = done on device d (one process per GPU is how the package runs, but nothing here may
 // break the day one process drives two).  Races between host threads are benign: the set-up is idempotent.

@@ -265,11 +265,15 @@ extern "C" int32_t vipant_layernorm_fwd(const void* x, int64_t ldx, const float*
                                         float* y_f32, float* mean, float* rstd, int64_t M, int64_t D, const uint16_t* add,
                                         void* sum_out, uint8_t* q, uint8_t* qscale, int32_t stream_flags, void* stream) {
     VIPANT_REQUIRE((q == nullptr) == (qscale == nullptr), VIPANT_EBADSHAPE, "layernorm_fwd: q and qscale go together");
-    VIPANT_REQUIRE(M > 0 && D > 0 && D % 256 == 0 && D <= 1024, VIPANT_EBADSHAPE,
-                   "layernorm_fwd: D must be a multiple of 256 up to 1024 (D=%ld)", (long)D);
+    VIPANT_REQUIRE(M > 0 && ln_width_ok(D), VIPANT_EBADSHAPE,
+                   "layernorm_fwd: D must be a multiple of 64 from 192 to 1024 (D=%ld)", (long)D);
+    VIPANT_REQUIRE(q == nullptr || ln_width_has_e4m3(D), VIPANT_EBADSHAPE,
+                   "layernorm_fwd: the e4m3 output exists at D = 256, 512, 768 and 1024 only (D=%ld)", (long)D);
     const bool in16 = (stream_flags & VIPANT_STREAM_IN_F16) != 0, out16 = (stream_flags & VIPANT_STREAM_OUT_F16) != 0;
     VIPANT_REQUIRE(ldx >= D && ldx % 4 == 0 && (uintptr_t)x % (in16 ? 8 : 16) == 0, VIPANT_EALIGN, "layernorm_fwd: bad ldx/alignment");
     hipStream_t s = (hipStream_t)stream;
+    if (!ln_width_has_e4m3(D))           // 64 H, H % 4 != 0: the lane-group kernels of layernorm_widths.hip
+        return ln_widths_fwd(x, ldx, gamma, beta, (bf16_t*)y, y_f32, mean, rstd, M, D, (const bf16_t*)add, sum_out, in16, out16, s);
     // one row per wave, no grid-stride loop: 254 us against 286 us with 2048 persistent workgroups at M = 161 792 (1.49 GB)
     const int blocks = (int)(ceil_div(M, 4) > (1 << 20) ? (1 << 20) : ceil_div(M, 4));
 #define LN_FWD_Q(NV, XI, XO, Q)                                                                                                 \
@@ -310,8 +314,10 @@ extern "C" int32_t vipant_layernorm_bwd(const void* dy, int32_t flags, const voi
                                         int64_t M, int64_t D, void* workspace, size_t workspace_bytes, uint8_t* q, uint8_t* qscale,
                                         void* stream) {
     VIPANT_REQUIRE((q == nullptr) == (qscale == nullptr), VIPANT_EBADSHAPE, "layernorm_bwd: q and qscale go together");
-    VIPANT_REQUIRE(M > 0 && D > 0 && D % 256 == 0 && D <= 1024, VIPANT_EBADSHAPE,
-                   "layernorm_bwd: D must be a multiple of 256 up to 1024 (D=%ld)", (long)D);
+    VIPANT_REQUIRE(M > 0 && ln_width_ok(D), VIPANT_EBADSHAPE,
+                   "layernorm_bwd: D must be a multiple of 64 from 192 to 1024 (D=%ld)", (long)D);
+    VIPANT_REQUIRE(q == nullptr || ln_width_has_e4m3(D), VIPANT_EBADSHAPE,
+                   "layernorm_bwd: the e4m3 output exists at D = 256, 512, 768 and 1024 only (D=%ld)", (long)D);
     VIPANT_REQUIRE(ldx >= D && ldx % 4 == 0 && lddx >= D && lddx % 4 == 0, VIPANT_EALIGN, "layernorm_bwd: bad strides");
     VIPANT_REQUIRE(workspace != nullptr && workspace_bytes >= vipant_layernorm_bwd_workspace_bytes(M, D),
                    VIPANT_ENOWORKSPACE, "layernorm_bwd: workspace too small");
@@ -322,6 +328,15 @@ extern "C" int32_t vipant_layernorm_bwd(const void* dy, int32_t flags, const voi
     VIPANT_REQUIRE(!(dres_bf16 && (dres == nullptr || dy_is_f32)), VIPANT_EBADSHAPE,
                    "layernorm_bwd: a bf16 residual gradient needs dres and a bf16 dy");
     const bool x16 = (flags & VIPANT_LN_X_F16) != 0;
+    if (!ln_width_has_e4m3(D)) {         // 64 H, H % 4 != 0: the lane-group kernel of layernorm_widths.hip, the same finalize
+        const int32_t rc = ln_widths_bwd(dy, dy_is_f32, dres_bf16, x16, x, ldx, mean, rstd, gamma, dres, dx_f32, lddx,
+                                         (bf16_t*)dx_bf16, partial, blocks, M, D, s);
+        if (rc != VIPANT_OK) return rc;
+        hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((unsigned)ceil_div(3 * D, 64)), dim3(1024), 0, s, (const float*)partial,
+                           blocks, (int)D, dgamma, dbeta, dx_colsum, accumulate);
+        VIPANT_LAUNCH_CHECK();
+        return VIPANT_OK;
+    }
 #define LN_BWD_Q(NV, A, B, XT, Q)                                                                                                 \
     hipLaunchKernelGGL((ln_bwd_kernel<NV, A, B, XT, 4, Q>), dim3(blocks), dim3(256), 0, s, dy, (const XT*)x, ldx, mean, rstd, gamma, \
                        dres, dx_f32, lddx, (bf16_t*)dx_bf16, partial, M, q, qscale)

@@ -29,6 +29,15 @@ def build_encoder_module(cfg, **kwargs):
     return ENCODER_MODULES_REGISTRY.get(cfg.name)(cfg, **kwargs)
 
 
+def check_tower_width(width, who):
+    """A transformer tower's width is 64 H with 3 <= H <= 16 (heads of 64; the widths vipant_layernorm_fwd / _bwd take): anything
+    else is refused when the module is built, not by the first launch."""
+    if width % 64 != 0 or not 192 <= width <= 1024:
+        from ..errors import VipantError
+        raise VipantError(f"{who}: width = {width} is not a multiple of 64 from 192 to 1024 (3 to 16 heads of 64: the widths the "
+                          "LayerNorm kernels take)")
+
+
 class LayerNorm(nn.LayerNorm):
     """Parameter container for ln_* (clip/model.py:154-160); the fp32-statistics LayerNorm itself is
     vipant_layernorm_fwd/bwd."""
@@ -124,6 +133,7 @@ class GPTPreEncoder(MetaEncoder):
 
     def __init__(self, cfg, width=512, ctx_len=77, **kwargs):
         super().__init__()
+        check_tower_width(width, "GPTPreEncoder")
         self.position_resolution = (ctx_len, width)
         self.token_embedding = nn.Embedding(cfg.vocab_size, width)
         self.initialize_parameters()
@@ -148,6 +158,7 @@ class GPTPostEncoder(MetaEncoder):
 
     def __init__(self, cfg, width=512, embed_dim=512, **kwargs):
         super().__init__()
+        check_tower_width(width, "GPTPostEncoder")
         scale = width ** -0.5
         self.ln = LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, embed_dim))
@@ -225,6 +236,7 @@ class ViTPreEncoder(MetaEncoder):
 
     def __init__(self, cfg, width=768, resolution=224, **kwargs):
         super().__init__()
+        check_tower_width(width, "ViTPreEncoder")
         self.stride, _, self.position_resolution = _vit_position_resolution(resolution, cfg.patch_size, cfg.stride)
         self.position_resolution += (width,)
         self.conv1 = nn.Conv2d(in_channels=cfg.in_channels, out_channels=width, kernel_size=cfg.patch_size,
@@ -271,6 +283,7 @@ class ViTPostEncoder(MetaEncoder):
 
     def __init__(self, cfg, width=768, embed_dim=512, **kwargs):
         super().__init__()
+        check_tower_width(width, "ViTPostEncoder")
         scale = width ** -0.5
         self.ln = LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, embed_dim))
@@ -324,6 +337,8 @@ class TransformerBackbone(MetaEncoder):
         super().__init__()
         self.batch_first = True     # token-major batch-first kernels: MetaHead skips its permutes
         self.ctx_len = ctx_len
+        check_tower_width(width, "TransformerBackbone")
+        self.width = width
         heads = width // 64
         attn_mask = self.build_attention_mask()
         self.resblocks = nn.Sequential(*[
@@ -335,6 +350,20 @@ class TransformerBackbone(MetaEncoder):
         self.fp8 = False            # `running.fp8_gemm`: e4m3 operands in the NT contractions of the trainable blocks (configs[4])
         self.stream_f16 = True      # `running.stream_dtype` (fp16 | fp32): residual stream inside the stack in the reference's autocast precision
         self.last_block_rows = True     # `running.last_block_rows`: honour `rows=` (the last block on the read-out rows only; exact)
+
+    @property
+    def fp8(self):
+        return self._fp8
+
+    @fp8.setter
+    def fp8(self, on):
+        """The e4m3 forms of the LayerNorm outputs exist in the kernels for the multiples of 256 only: an e4m3 tower of another
+        width is refused here, when the tower is configured."""
+        if on and self.width not in (256, 512, 768, 1024):
+            from ..errors import VipantError
+            raise VipantError(f"running.fp8_gemm=True: a tower of width {self.width} has no e4m3 kernels; the widths with e4m3 towers "
+                              "are 256, 512, 768 and 1024")
+        self._fp8 = bool(on)
 
     def build_attention_mask(self):
         """Marker only: the -inf upper-triangular mask (val.py:484-491) is applied inside the attention kernel."""
