@@ -378,6 +378,27 @@ int32_t vipant_infonce_multi_fwd_bwd(const float* const* x, int32_t nop, const i
                                      int64_t E, int64_t row0, int64_t nrows, void* workspace, size_t workspace_bytes,
                                      void* stream);
 
+/* ---- Pairwise sigmoid contrastive loss (SigLIP; SigmoidLossHead) --------------------------------------
+ * x1, x2 fp32 [B, E] (L2-normalised); logit_scale, logit_bias: DEVICE scalars, the raw parameters.
+ *   s = min(exp(logit_scale), scale_max) (scale_max <= 0: no clamp);  z_ij = s <x1_i, x2_j> + logit_bias;  y_ij = +1 if i == j else -1;
+ *   loss = (1/B) sum_ij softplus(-y_ij z_ij);  G_ij = -y_ij sigmoid(-y_ij z_ij) / B;  dx1 = s G x2;  dx2 = s G^T x1;
+ *   dlogit_bias = sum_ij G_ij;  dlogit_scale = s sum_ij G_ij <x1_i, x2_j> (0 where the clamp is active).
+ * dx1, dx2 fp32 [nrows, E] are the rows [row0, row0 + nrows) (dx1: the strip's rows of G, dx2: its columns), scaled by grad_scale, as
+ * are dlogit_scale and dlogit_bias; any of the four gradient pointers may be NULL.
+ * STRIP CONVENTION: loss, dlogit_scale and dlogit_bias are the sums over the strip's ROWS of the pair matrix (i in the strip, all j),
+ * still normalised by 1/B: the full-batch values when nrows == B; the values of strips that partition the batch add up to them (the
+ * replicas sum them on the host side), and no tile outside the strip's rows and columns is walked.
+ * One pass at every B: logits at fp32 grade (bf16 hi/lo split on MFMA), G as a bf16 MFMA operand held in registers, nothing B x B or
+ * nrows x B stored; workspace = bf16 operand copies (12 B E bytes) + 16 bytes per 16 strip rows.  Deterministic (no atomics).
+ * B >= 1, E % 64 == 0, 64 <= E <= 1024, 0 < nrows, row0 + nrows <= B; anything else is refused before any launch (VIPANT_EBADSHAPE /
+ * VIPANT_ENOWORKSPACE / VIPANT_EALIGN: workspace 256-byte, dx1 / dx2 16-byte aligned).  The workspace query returns 0 for a shape the
+ * call refuses.  No allocation and no synchronisation in the call. */
+size_t vipant_sigmoid_loss_workspace_bytes(int64_t B, int64_t E, int64_t nrows);
+int32_t vipant_sigmoid_loss_fwd_bwd(const float* x1, const float* x2, const float* logit_scale, const float* logit_bias,
+                                    float scale_max, float* loss, float* dx1, float* dx2, float* dlogit_scale,
+                                    float* dlogit_bias, float grad_scale, int64_t B, int64_t E, int64_t row0, int64_t nrows,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Retrieval evaluation (LossHead.report / retrieval_eval, cvap/module/decoder/loss_head.py:71-168) ----
  * x1 fp32 [N1, E] queries, x2 fp32 [N2, E] candidates (both L2-normalised by the caller), gold int32 [N1, G]
  * with entries in [0, N2).  Replaces `(x1 @ x2.t()).argsort(descending=True)` + `torch.where(ind == label)`:

@@ -150,6 +150,8 @@ GROUPS = {
     },
     "model/loss": {
         "ce": {"name": "CELossHead", "layers": [], "scaling": True, "scale_max": None},
+        # pairwise sigmoid loss (SigLIP): temperature exp(logit_scale) from scale_init, additive logit_bias from bias_init
+        "sigmoid": {"name": "SigmoidLossHead", "layers": [], "scaling": True, "scale_max": None, "scale_init": 10.0, "bias_init": -10.0},
         "ce_val": {"name": "VALCELossHead", "layers": [], "scaling": True, "scale_max": None,
                    "va": True, "lv": False, "al": True},
         # configs/model/loss/ce_va.yaml: v = image view 1, p = the precomputed ("prime") image features, a = audio

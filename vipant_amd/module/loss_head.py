@@ -222,6 +222,46 @@ class CELossHead(LossHead):
         return ops.InfoNCEFn.apply(x1, x2, ls, scale_max, 0, b, 1.0 / parallel.world_size() if parallel.active() else 1.0)
 
 
+@MORE_LOSS_HEADS_REGISTRY.register()
+class SigmoidLossHead(CELossHead):
+    """Pairwise sigmoid contrastive loss (SigLIP): every pair (i, j) of the batch is a binary problem, positive on the diagonal, with a
+    learnable temperature and bias -- loss = (1/B) sum_ij softplus(-y_ij (exp(logit_scale) <x1_i, x2_j> + logit_bias)).  No
+    normaliser couples the pairs, so the fused call (ops.SigmoidLossFn) finishes loss and every gradient in one walk of the pair
+    matrix, and under replicas with global negatives a rank walks only its strip: its loss and parameter gradients are partial sums
+    that the ranks add (two scalar collectives).  Evaluation (`infer`, `report`) is CELossHead's: the ranks do not depend on the bias."""
+
+    def __init__(self, cfg, **kwargs):
+        super().__init__(cfg, **kwargs)
+        scale_init, bias_init = float(getattr(cfg, "scale_init", 10.0)), float(getattr(cfg, "bias_init", -10.0))
+        if cfg.scaling:
+            self.logit_scale = nn.Parameter(torch.ones([]) * np.log(scale_init))
+            self.logit_bias = nn.Parameter(torch.ones([]) * bias_init)
+        else:
+            self.logit_bias = torch.zeros([], requires_grad=False)
+
+    def copy_state_dict(self, state_dict):
+        new_dict = self.state_dict()
+        new_dict.update({k: state_dict[k] for k in ("logit_scale", "logit_bias") if k in new_dict and k in state_dict})
+        self.load_state_dict(new_dict)
+
+    def forward(self, x1, x2, *args, **kwargs):
+        if not self.training:
+            return super().forward(x1, x2, *args, **kwargs)
+        if not kwargs.get("normalized", False):
+            x1, x2 = ops.L2NormFn.apply(x1), ops.L2NormFn.apply(x2)
+        scale_max = 0.0 if self.scale_max == float("inf") else float(self.scale_max)
+        learn = isinstance(self.logit_scale, nn.Parameter)
+        ls, lb = (self.logit_scale, self.logit_bias) if learn else (self.logit_scale.to(x1.device), self.logit_bias.to(x1.device))
+        b = x1.shape[0]
+        if parallel.active() and self.negatives == "global":
+            x1g, x2g = parallel.all_gather_features(x1, x2)
+            if learn:
+                ls, lb = parallel.complete_scalar_grads(ls, lb)
+            part = ops.SigmoidLossFn.apply(x1g, x2g, ls, lb, scale_max, parallel.rank() * b, b, 1.0)
+            return parallel.sum_partial_loss(part)
+        return ops.SigmoidLossFn.apply(x1, x2, ls, lb, scale_max, 0, b, 1.0 / parallel.world_size() if parallel.active() else 1.0)
+
+
 @LOSS_HEADS_REGISTRY.register()
 class VALCELossHead(LossHead):
     """Sum of pairwise InfoNCE heads over {vision, audio, language} (loss_head.py:421-495); the AT script

@@ -1219,6 +1219,57 @@ class InfoNCEFn(torch.autograd.Function):
                 (dls if unit else dls * dloss).reshape(ls_shape) if need[2] else None, None, None, None, None)
 
 
+class SigmoidLossFn(torch.autograd.Function):
+    """Pairwise sigmoid contrastive loss (SigmoidLossHead.forward) on L2-normalised fp32 features: one fused call
+    (vipant_sigmoid_loss_fwd_bwd) in the forward, which leaves every gradient; the backward scales them.
+
+    x1, x2: [B, E] -- the (all-gathered) global batch.  Feature gradients are produced for rows [row0, row0 + nrows) only; the loss
+    and the gradients of `logit_scale` / `logit_bias` are the sums over the strip's rows of the pair matrix, normalised by 1/B: the
+    full-batch values when nrows == B, and values that ADD UP to them over the strips of a replica group (include/vipant_hip.h).
+    `grad_scale` pre-multiplies every gradient."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, logit_scale, logit_bias, scale_max, row0, nrows, grad_scale):
+        _need(x1, F32, "sigmoid_loss.x1"); _need(x2, F32, "sigmoid_loss.x2")
+        x1, x2 = x1.contiguous(), x2.contiguous()
+        B, E = x1.shape
+        dev = x1.device
+        need = ctx.needs_input_grad
+        want = need[0] or need[1] or need[2] or need[3]
+        nbytes = query("vipant_sigmoid_loss_workspace_bytes", B, E, int(nrows))
+        ws = scratch("sigmoid_loss", max(nbytes, 256), dev)
+        loss = torch.empty((1,), dtype=F32, device=dev)
+        d1 = torch.empty((nrows, E), dtype=F32, device=dev) if want else None
+        d2 = torch.empty((nrows, E), dtype=F32, device=dev) if want else None
+        dsc = torch.empty((2,), dtype=F32, device=dev) if want else None       # dlogit_scale, dlogit_bias
+        ls, lb = _ls_scalar(logit_scale, dev), _ls_scalar(logit_bias, dev)
+        call("vipant_sigmoid_loss_fwd_bwd", x1.data_ptr(), x2.data_ptr(), ls.data_ptr(), lb.data_ptr(), float(scale_max or 0.0),
+             loss.data_ptr(), _ptr(d1), _ptr(d2), _ptr(dsc), dsc.data_ptr() + 4 if want else None, float(grad_scale), B, E, int(row0),
+             int(nrows), ws.data_ptr(), nbytes, _stream())
+        if want:
+            ctx.save_for_backward(d1, d2, dsc)
+            ctx.meta = (B, E, int(row0), int(nrows), tuple(logit_scale.shape), tuple(logit_bias.shape))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        d1, d2, dsc = ctx.saved_tensors
+        B, E, row0, nrows, ls_shape, lb_shape = ctx.meta
+        need = ctx.needs_input_grad
+        unit = dloss.dim() == 0 and dloss.data_ptr() == unit_grad(dloss.device).data_ptr()      # the trainer's cached 1.0
+
+        def expand(d):
+            if row0 == 0 and nrows == B:
+                return d if unit else d * dloss
+            full = torch.zeros((B, E), dtype=F32, device=d.device)
+            full[row0:row0 + nrows] = d * dloss
+            return full
+        if not unit:
+            dsc = dsc * dloss
+        return (expand(d1) if need[0] else None, expand(d2) if need[1] else None, dsc[0].reshape(ls_shape) if need[2] else None,
+                dsc[1].reshape(lb_shape) if need[3] else None, None, None, None, None)
+
+
 class InfoNCEMultiMeta:
     """The non-tensor arguments of InfoNCEMultiFn: `pairs` [(a, b)] indexes the operand list, `scale_max` / `weights` are per pair;
     rows [row0, row0 + nrows) get gradients, pre-multiplied by `grad_scale` (InfoNCEFn's conventions).  After the forward

@@ -78,6 +78,53 @@ def all_gather_features(*xs: torch.Tensor):
     return tuple(packed[:, i * E:(i + 1) * E].contiguous() for i in range(len(xs)))
 
 
+def _sum_small(t: torch.Tensor) -> torch.Tensor:
+    """SUM over the ranks of a few scalars (gloo cannot reduce device tensors: staged through the host, as the gather above)."""
+    if t.is_cuda and dist.get_backend() == "gloo":
+        host = t.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM)
+        return host.to(t.device)
+    t = t.clone()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
+class _SumLoss(torch.autograd.Function):
+    """A loss that is a sum of per-rank partial sums: forward = SUM over the ranks, backward = identity (a rank's partial sum is
+    the only path from the total to its own inputs)."""
+
+    @staticmethod
+    def forward(ctx, partial):
+        return _sum_small(partial.reshape(1)).reshape(partial.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+class _SumScalarGrads(torch.autograd.Function):
+    """Identity on a few scalar parameters whose gradients arrive as per-rank partial sums: the backward SUMs them over the ranks in
+    one collective, so that each rank ends up with the complete gradient -- what the trainers assume of a loss head's parameters
+    under global negatives (they are left out of the gradient all-reduce)."""
+
+    @staticmethod
+    def forward(ctx, *ps):
+        return tuple(p.clone() for p in ps)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        flat = _sum_small(torch.stack([g.reshape(()) for g in gs]))
+        return tuple(flat[i].reshape(g.shape) for i, g in enumerate(gs))
+
+
+def sum_partial_loss(partial: torch.Tensor) -> torch.Tensor:
+    return _SumLoss.apply(partial)
+
+
+def complete_scalar_grads(*ps: torch.Tensor):
+    return _SumScalarGrads.apply(*ps)
+
+
 class GradSync:
     """SUM all-reduce of gradient buckets on a side stream: per block, overlapping the backward (`overlap="block"`), or all of a
     step's block buckets as one collective when the backward is over (`overlap="step"`)."""
