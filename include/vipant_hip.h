@@ -399,6 +399,28 @@ int32_t vipant_sigmoid_loss_fwd_bwd(const float* x1, const float* x2, const floa
                                     float* dlogit_bias, float grad_scale, int64_t B, int64_t E, int64_t row0, int64_t nrows,
                                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Label-aware InfoNCE: rows that share a group id are positives of each other (LabelCELossHead) ------
+ * x1, x2 fp32 [B, E] (L2-normalised); groups int32 [B] or NULL; logit_scale: DEVICE scalar, the raw parameter.
+ *   s = min(exp(logit_scale), scale_max) (scale_max <= 0: no clamp);  z_ij = s <x1_i, x2_j>;
+ *   P_ij = 1 if i == j or groups[i] == groups[j] >= 0, else 0 (a negative id: "no label", positive with itself only; NULL: P = I);
+ *   n_i = sum_j P_ij (P is symmetric: row and column counts agree);
+ *   loss = (1/B) sum_i [ lse_j z_ij - (1/n_i) sum_j P_ij z_ij ] + (1/B) sum_j [ lse_i z_ij - (1/n_j) sum_i P_ij z_ij ];
+ *   G_ij = ( exp(z_ij - rlse_i) + exp(z_ij - clse_j) - 2 P_ij / n_i ) / B;  dx1 = s G x2;  dx2 = s G^T x1;
+ *   dlogit_scale = sum_ij G_ij z_ij (0 where the clamp is active).  With P = I this is vipant_infonce_fwd_bwd's loss.
+ * STRIP CONVENTION (vipant_infonce_fwd_bwd's): loss and dlogit_scale are the full-batch values on every caller; dx1, dx2 fp32
+ * [nrows, E] are the rows [row0, row0 + nrows); dx1, dx2 and dlogit_scale are scaled by grad_scale.  dlogit_scale is written
+ * whenever it is non-NULL; NULL dx1 / dx2 are not computed, and with both NULL or nrows == 0 there is no gradient walk.
+ * Two walks of the pair matrix at every B (statistics over the batch, gradients over the strip): logits at fp32 grade at every pair
+ * (bf16 hi/lo split on MFMA), G as a bf16 MFMA operand held in registers, nothing B x B or nrows x B stored; workspace = bf16 operand
+ * copies (12 B E bytes) + 16 bytes per row.  Deterministic (no atomics, every sum in a fixed order).
+ * B >= 1, E % 64 == 0, 64 <= E <= 1024, 0 <= nrows, 0 <= row0, row0 + nrows <= B; anything else is refused before any launch, writing
+ * nothing (VIPANT_EBADSHAPE / VIPANT_ENOWORKSPACE for a NULL or short workspace / VIPANT_EALIGN: workspace 256-byte, dx1 / dx2 16-byte
+ * aligned).  The workspace query returns 0 for a shape the call refuses.  No allocation and no synchronisation in the call. */
+size_t vipant_label_nce_workspace_bytes(int64_t B, int64_t E, int64_t nrows);
+int32_t vipant_label_nce_fwd_bwd(const float* x1, const float* x2, const int32_t* groups, const float* logit_scale, float scale_max,
+                                 float* loss, float* dx1, float* dx2, float* dlogit_scale, float grad_scale, int64_t B, int64_t E,
+                                 int64_t row0, int64_t nrows, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Retrieval evaluation (LossHead.report / retrieval_eval, cvap/module/decoder/loss_head.py:71-168) ----
  * x1 fp32 [N1, E] queries, x2 fp32 [N2, E] candidates (both L2-normalised by the caller), gold int32 [N1, G]
  * with entries in [0, N2).  Replaces `(x1 @ x2.t()).argsort(descending=True)` + `torch.where(ind == label)`:

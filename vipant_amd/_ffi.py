@@ -130,6 +130,8 @@ PROTOTYPES = {
     "vipant_infonce_multi_fwd_bwd": (_i32, [_p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _f32, _i64, _i64, _i64, _i64, _p, _sz, _p]),
     "vipant_sigmoid_loss_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "vipant_sigmoid_loss_fwd_bwd": (_i32, [_p, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _f32, _i64, _i64, _i64, _i64, _p, _sz, _p]),
+    "vipant_label_nce_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "vipant_label_nce_fwd_bwd": (_i32, [_p, _p, _p, _p, _f32, _p, _p, _p, _p, _f32, _i64, _i64, _i64, _i64, _p, _sz, _p]),
     "vipant_retrieval_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "vipant_retrieval_ranks": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _sz, _p]),
     "vipant_tagging_stats_workspace_bytes": (_sz, [_i64, _i64]),

@@ -154,6 +154,11 @@ GROUPS = {
         "sigmoid": {"name": "SigmoidLossHead", "layers": [], "scaling": True, "scale_max": None, "scale_init": 10.0, "bias_init": -10.0},
         "ce_val": {"name": "VALCELossHead", "layers": [], "scaling": True, "scale_max": None,
                    "va": True, "lv": False, "al": True},
+        # label-aware InfoNCE: rows of the batch that share a label id are positives of each other (LabelCELossHead; under
+        # +running.audioset_text=True the id is the label whose prompt the clip was shown); ce_val_label: on the listed pairs only
+        "ce_label": {"name": "LabelCELossHead", "layers": [], "scaling": True, "scale_max": None},
+        "ce_val_label": {"name": "VALCELossHead", "layers": [], "scaling": True, "scale_max": None,
+                         "va": True, "lv": False, "al": True, "label_positives": ["al"]},
         # configs/model/loss/ce_va.yaml: v = image view 1, p = the precomputed ("prime") image features, a = audio
         "ce_va": {"name": "VACELossHead", "layers": [], "scaling": True, "scale_max": None,
                   "vp": True, "vp_w": 1., "ap": False, "ap_w": 1., "va": True, "va_w": 1., "vv": True, "vv_w": 1.,

@@ -28,8 +28,9 @@ class CVALP(nn.Module):
 
     # ------------------------------------------------------------------ forward (cvalp.py:34-62)
     def forward(self, images, audios, text, *args, **kwargs):
+        groups = kwargs.get("groups", None)
         kwargs = {"normalized": self.loss_head.normalized, "names": kwargs.get("names", None)}
-        return self.loss_from_features(*self.features(images, audios, text, **kwargs), **kwargs)
+        return self.loss_from_features(*self.features(images, audios, text, **kwargs), groups=groups, **kwargs)
 
     def features(self, images, audios, text, **kwargs):
         """The three towers (cvalp.py:37-59) -> (image, audio, text) features, None for a modality that is absent or dummy.
@@ -71,7 +72,10 @@ class CVALP(nn.Module):
         return image_features, audio_features, text_features
 
     def loss_from_features(self, image_features, audio_features, text_features, **kwargs):
+        groups = kwargs.get("groups", None)
         kwargs = {"normalized": self.loss_head.normalized, "names": kwargs.get("names", None)}
+        if groups is not None:          # the batch's label ids, for a loss head with label positives (LabelCELossHead)
+            kwargs["groups"] = groups
         return self.loss_head(image_features, audio_features, text_features, **kwargs)
 
     @staticmethod

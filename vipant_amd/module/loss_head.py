@@ -262,23 +262,54 @@ class SigmoidLossHead(CELossHead):
         return ops.SigmoidLossFn.apply(x1, x2, ls, lb, scale_max, 0, b, 1.0 / parallel.world_size() if parallel.active() else 1.0)
 
 
+@MORE_LOSS_HEADS_REGISTRY.register()
+class LabelCELossHead(CELossHead):
+    """Label-aware InfoNCE (the bidirectional multi-positive form of UniCL / SupCon): every row of the batch whose group id equals
+    row i's is a positive of row i and the soft-max target is uniform over them -- what AudioSet label prompts need, where dozens of
+    clips of a batch share one prompt and so one text feature.  `groups` int [b]: the label the clip's prompt was drawn from; a
+    negative id or `groups=None` leaves a row positive with itself only (None: CELossHead's loss).  One fused call
+    (ops.LabelNCEFn); under replicas with global negatives the ids are gathered with the features and a rank takes its strip, as
+    CELossHead does.  Evaluation (`infer`, `report`) is CELossHead's."""
+    wants_groups = True
+
+    def forward(self, x1, x2, *args, groups=None, **kwargs):
+        if not self.training:
+            return super().forward(x1, x2, *args, **kwargs)
+        if not kwargs.get("normalized", False):
+            x1, x2 = ops.L2NormFn.apply(x1), ops.L2NormFn.apply(x2)
+        scale_max = 0.0 if self.scale_max == float("inf") else float(self.scale_max)
+        ls = self.logit_scale if isinstance(self.logit_scale, nn.Parameter) else self.logit_scale.to(x1.device)
+        b = x1.shape[0]
+        if parallel.active() and self.negatives == "global":
+            x1g, x2g = parallel.all_gather_features(x1, x2)
+            ids = None if groups is None else parallel.all_gather_ids(groups.to(x1.device))
+            return ops.LabelNCEFn.apply(x1g, x2g, ids, ls, scale_max, parallel.rank() * b, b, 1.0)
+        return ops.LabelNCEFn.apply(x1, x2, groups, ls, scale_max, 0, b, 1.0 / parallel.world_size() if parallel.active() else 1.0)
+
+
 @LOSS_HEADS_REGISTRY.register()
 class VALCELossHead(LossHead):
     """Sum of pairwise InfoNCE heads over {vision, audio, language} (loss_head.py:421-495); the AT script
-    enables only `al`."""
+    enables only `al`.  Optional key `label_positives`: the pairs among `va`, `lv`, `al` that are LabelCELossHeads and receive the
+    batch's `groups`; absent, every pair is a CELossHead."""
 
     def __init__(self, cfg, **kwargs):
         super().__init__()
         self.loss_head_va = self.loss_head_lv = self.loss_head_al = None
         self._total_loss = {}
+        labelled = [str(k) for k in (getattr(cfg, "label_positives", None) or [])]
+        if any(k not in ("va", "lv", "al") for k in labelled):
+            raise VipantError(f"model.loss.label_positives={labelled}: a list drawn from va, lv, al")
+        self.wants_groups = bool(labelled)
+        pair = lambda key: (LabelCELossHead if key in labelled else CELossHead)(cfg, **kwargs)
         if cfg.va:
-            self.loss_head_va = CELossHead(cfg, **kwargs)
+            self.loss_head_va = pair("va")
             self._total_loss.update({"va": 0.})
         if cfg.lv:
-            self.loss_head_lv = CELossHead(cfg, **kwargs)
+            self.loss_head_lv = pair("lv")
             self._total_loss.update({"lv": 0.})
         if cfg.al:
-            self.loss_head_al = CELossHead(cfg, **kwargs)
+            self.loss_head_al = pair("al")
             self._total_loss.update({"al": 0.})
 
     def copy_state_dict(self, state_dict):
@@ -303,7 +334,7 @@ class VALCELossHead(LossHead):
                 out.append(f"{tag}: " + head.report(gold_file))
         return "\n" + "\n".join(out).strip()
 
-    def forward(self, x1, x2, x3, *args, **kwargs):
+    def forward(self, x1, x2, x3, *args, groups=None, **kwargs):
         """v: x1; a: x2; l: x3."""
         if not self.training:
             if not dist.is_initialized() or dist.get_rank() == 0:
@@ -312,7 +343,7 @@ class VALCELossHead(LossHead):
         loss = 0.0
         for key, head, a, b in self._pairs(x1, x2, x3):
             if a is not None and b is not None and head is not None:
-                term = head(a, b, *args, **kwargs)
+                term = head(a, b, *args, groups=groups, **kwargs) if isinstance(head, LabelCELossHead) else head(a, b, *args, **kwargs)
                 self._total_loss[key] += term.detach()
                 loss = loss + term
         return loss

@@ -128,8 +128,16 @@ def _synthetic_prompts(seed, nclass):
     return [t + [0] * (width - len(t)) for t in prompts]
 
 
+def label_positives(cfg) -> bool:
+    """Does the configured loss head take the batch's label ids as groups of positives (`model/loss=ce_label`: LabelCELossHead;
+    `ce_val_label`: VALCELossHead with `label_positives`)?"""
+    loss = getattr(getattr(cfg, "model", None), "loss", None)
+    return loss is not None and (getattr(loss, "name", None) == "LabelCELossHead" or bool(getattr(loss, "label_positives", None)))
+
+
 class Monitor(object):
     with_text = True      # VALMonitor (AT); VAMonitor sets False
+    label_groups = False            # the batches' labels are real label ids AND the loss head wants them as groups of positives
     partial_head_grads = False      # a classification head scores a rank's own rows: its gradients join the replica reduction
     norms_only = False              # `running.audio.eval_norms` on a file dataset: the statistics are the run's only task
 
@@ -151,6 +159,8 @@ class Monitor(object):
         self._configure(model)
         self.model.train(not cfg.eval)
         self.build_optimizer(tunable_params)
+        if getattr(model.loss_head, "wants_groups", False) and not self.label_groups:
+            self.echo("The loss head takes label positives, but these batches carry no label ids: it runs with identity positives.")
 
     def _configure(self, model):
         """Run-time switches of the towers (`running.*`) and, under replicas, the gradient reduction they feed."""
@@ -263,6 +273,11 @@ class Monitor(object):
         evaluation and test loaders whose index exists."""
         from .data import build_audioset_label_map, build_audioset_text_dataloader, build_filter_set
         rcfg = self.cfg.running
+        if label_positives(self.cfg):       # the default text mode ships the label whose prompt the clip is shown; the other two ship 0
+            if rcfg.get("cat_label", False) or rcfg.get("text_emb", None) is not None:
+                raise VipantError("a loss head with label positives (model/loss=ce_label, ce_val_label) needs the label of each clip's prompt: "
+                                  "running.cat_label and running.text_emb label every clip 0, which would make the whole batch one group")
+            self.label_groups = True
         external_text = None
         if rcfg.get("text_emb", None) is not None:
             text_file = f"{rcfg.data_root}/caption/{rcfg.text_emb}.csv"
@@ -430,7 +445,7 @@ class Monitor(object):
             self.last_time = this_time
 
     # ------------------------------------------------------------------ one optimisation step
-    def _forward_backward_micro(self, images, audios, text, mb):
+    def _forward_backward_micro(self, images, audios, text, mb, **extra):
         """One global-batch step with the towers run `mb` samples at a time (`running.micro_batch`), for batches whose
         activations do not fit at once (BASELINE.json configs[4]: ViT-L, 1024 clips per GPU).  The objective is untouched --
         every sample is still scored against the whole batch:
@@ -450,7 +465,7 @@ class Monitor(object):
                 and any(p.requires_grad for p in heads[m].parameters())]
         for m in live:
             feats[m].requires_grad_()
-        loss = self.model.loss_from_features(*feats)
+        loss = self.model.loss_from_features(*feats, **extra)
         loss.backward()
         if not live:                       # every tower frozen: only the loss head trains, nothing to re-run
             return loss
@@ -473,14 +488,16 @@ class Monitor(object):
         self._micro_step = True
         return loss
 
-    def step(self, images, audios, text):
-        """zero_grad -> forward -> backward -> (replica gradient reduction) -> optimizer (cvalp.py:200-205)."""
+    def step(self, images, audios, text, groups=None):
+        """zero_grad -> forward -> backward -> (replica gradient reduction) -> optimizer (cvalp.py:200-205).  groups int [b]: the
+        batch's label ids for a loss head with label positives (`_step_inputs` passes them only when they are real)."""
         self.optimizer.zero_grad(set_to_none=True)
         mb = int(self.cfg.running.get("micro_batch", 0) or 0)
+        extra = {} if groups is None else {"groups": groups}
         if 0 < mb < audios.shape[0]:
-            loss = self._forward_backward_micro(images, audios, text if self.with_text else None, mb)
+            loss = self._forward_backward_micro(images, audios, text if self.with_text else None, mb, **extra)
         else:
-            loss = self.model(images, audios, text if self.with_text else None)
+            loss = self.model(images, audios, text if self.with_text else None, **extra)
             self._backward(loss)
         self._reduce_and_update()
         return loss
@@ -506,8 +523,8 @@ class Monitor(object):
 
     def _step_inputs(self, batch):
         """What `make_batch` returned -> (the arguments of `step`, the number of samples in the batch)."""
-        images, audios, text, _, _ = batch
-        return (images, audios, text), images.shape[0]
+        images, audios, text, labels, _ = batch
+        return (images, audios, text, labels) if self.label_groups else (images, audios, text), images.shape[0]
 
     # ------------------------------------------------------------------ cvalp.py:172-272
     def epoch(self, iepoch):

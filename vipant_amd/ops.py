@@ -1203,20 +1203,66 @@ class InfoNCEFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss):
-        d1, d2, dls = ctx.saved_tensors
-        B, E, row0, nrows, ls_shape = ctx.meta
+        return (*_nce_backward(ctx, dloss, ctx.needs_input_grad[:3]), None, None, None, None)
+
+
+def _nce_backward(ctx, dloss, need):
+    """The backward of InfoNCEFn and LabelNCEFn: the strip's gradient rows, saved by the forward, scaled and expanded to [B, E];
+    `need` = does (x1, x2, logit_scale) want a gradient."""
+    d1, d2, dls = ctx.saved_tensors
+    B, E, row0, nrows, ls_shape = ctx.meta
+    unit = dloss.dim() == 0 and dloss.data_ptr() == unit_grad(dloss.device).data_ptr()      # the trainer's cached 1.0
+
+    def expand(d):
+        if row0 == 0 and nrows == B:         # one replica: the slice is the batch (one launch instead of fill + mul + copy)
+            return d if unit else d * dloss
+        full = torch.zeros((B, E), dtype=F32, device=d.device)
+        full[row0:row0 + nrows] = d * dloss
+        return full
+    return (expand(d1) if need[0] else None, expand(d2) if need[1] else None,
+            (dls if unit else dls * dloss).reshape(ls_shape) if need[2] else None)
+
+
+class LabelNCEFn(torch.autograd.Function):
+    """Label-aware InfoNCE (LabelCELossHead.forward) on L2-normalised fp32 features: rows that share a group id are positives of
+    each other, the soft-max target is uniform over them (vipant_label_nce_fwd_bwd, include/vipant_hip.h).
+
+    x1, x2: [B, E] -- the (all-gathered) global batch; groups: any integer tensor [B] (converted to int32 on the device; a negative
+    id = no label, positive with itself only) or None (identity positives: InfoNCEFn's loss).  Strip and `grad_scale` conventions
+    are InfoNCEFn's: full-batch loss and `logit_scale` gradient on every caller, feature gradients for rows [row0, row0 + nrows)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, groups, logit_scale, scale_max, row0, nrows, grad_scale):
+        _need(x1, F32, "label_nce.x1"); _need(x2, F32, "label_nce.x2")
+        x1, x2 = x1.contiguous(), x2.contiguous()
+        B, E = x1.shape
+        dev = x1.device
+        if groups is not None:
+            if groups.is_floating_point() or groups.dtype == torch.bool or tuple(groups.shape) != (B,):
+                raise _ffi.VipantError(f"label_nce.groups: need an integer tensor of shape ({B},), got {groups.dtype} {tuple(groups.shape)}")
+            groups = groups.to(device=dev, dtype=torch.int32).contiguous()
         need = ctx.needs_input_grad
+        want = need[0] or need[1] or need[3]
+        nbytes = query("vipant_label_nce_workspace_bytes", B, E, int(nrows))
+        ws = scratch("label_nce", max(nbytes, 256), dev)
+        loss = torch.empty((1,), dtype=F32, device=dev)
+        d1 = torch.empty((nrows, E), dtype=F32, device=dev) if want else None
+        d2 = torch.empty((nrows, E), dtype=F32, device=dev) if want else None
+        dls = torch.empty((1,), dtype=F32, device=dev) if want else None
+        ls = logit_scale.detach().reshape(1).to(F32)
+        call("vipant_label_nce_fwd_bwd", x1.data_ptr(), x2.data_ptr(), _ptr(groups), ls.data_ptr(), float(scale_max or 0.0),
+             loss.data_ptr(), _ptr(d1), _ptr(d2), _ptr(dls), float(grad_scale), B, E, int(row0), int(nrows), ws.data_ptr(), nbytes,
+             _stream())
+        if want:
+            ctx.save_for_backward(d1, d2, dls)
+            ctx.meta = (B, E, int(row0), int(nrows), tuple(logit_scale.shape))
+        return loss.reshape(())
 
-        unit = dloss.dim() == 0 and dloss.data_ptr() == unit_grad(dloss.device).data_ptr()      # the trainer's cached 1.0
-
-        def expand(d):
-            if row0 == 0 and nrows == B:         # one replica: the slice is the batch (one launch instead of fill + mul + copy)
-                return d if unit else d * dloss
-            full = torch.zeros((B, E), dtype=F32, device=d.device)
-            full[row0:row0 + nrows] = d * dloss
-            return full
-        return (expand(d1) if need[0] else None, expand(d2) if need[1] else None,
-                (dls if unit else dls * dloss).reshape(ls_shape) if need[2] else None, None, None, None, None)
+    @staticmethod
+    def backward(ctx, dloss):
+        need = ctx.needs_input_grad
+        g1, g2, gls = _nce_backward(ctx, dloss, (need[0], need[1], need[3]))
+        return (g1, g2, None, gls, None, None, None, None)
 
 
 class SigmoidLossFn(torch.autograd.Function):

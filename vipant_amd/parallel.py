@@ -78,6 +78,22 @@ def all_gather_features(*xs: torch.Tensor):
     return tuple(packed[:, i * E:(i + 1) * E].contiguous() for i in range(len(xs)))
 
 
+def all_gather_ids(ids: torch.Tensor) -> torch.Tensor:
+    """[b] integer ids per rank -> [world * b], in rank order (the rows of `all_gather_features`).  No gradient: ids are data."""
+    ids = ids.detach().contiguous()
+    w = world_size()
+    out = torch.empty((w * ids.shape[0],), dtype=ids.dtype, device=ids.device)
+    if ids.is_cuda and dist.get_backend() == "gloo":        # gloo cannot gather device tensors: staged through the host
+        host = torch.empty(out.shape, dtype=ids.dtype)
+        dist.all_gather(list(host.chunk(w)), ids.cpu())
+        out.copy_(host)
+    elif dist.get_backend() == "nccl":
+        dist.all_gather_into_tensor(out, ids)
+    else:
+        dist.all_gather(list(out.chunk(w)), ids)
+    return out
+
+
 def _sum_small(t: torch.Tensor) -> torch.Tensor:
     """SUM over the ranks of a few scalars (gloo cannot reduce device tensors: staged through the host, as the gather above)."""
     if t.is_cuda and dist.get_backend() == "gloo":
