@@ -796,6 +796,26 @@ int32_t vipant_bce_logits(const float* z, int64_t ldz, const uint8_t* targets, i
 int32_t vipant_bce_logits_soft(const float* z, int64_t ldz, const float* targets, int64_t ldt, const float* logit_scale, float* loss,
                                uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp, int64_t row0, int64_t nrows,
                                float grad_scale, int64_t B, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+/* Multi-label hinge tagging loss (vipant_amd/csrc/hinge.hip): BCHingeLossHead, cvap/module/decoder/loss_more.py:145-198 --
+ * nn.MultiLabelMarginLoss()(sigmoid(exp(ls) * z), convert_label(targets)), a row's positives Y being the NON-ZERO entries of its
+ * target row (label[i].nonzero(): a fractional mixup label is a mark, there are no soft hinge targets).  With p = sigmoid(s z),
+ * P = |Y|, N = C - P every margin 1 - p_j + p_i is >= 0, so the P x N pair sum is, exactly,
+ *   row_loss = ( P N - N sum_{j in Y} p_j + P sum_{i not in Y} p_i ) / C,   loss = sum over the scored rows of row_loss / B
+ *   dz_c = grad_scale * s / B * (c in Y ? -N : P) / C * p_c (1 - p_c),      dscale = sum over rows and classes of dz_c z_c
+ * and rows with P = 0 or P = C give 0.  No index lists, no pair walk.  Arguments as vipant_bce_logits, argument for argument, plus
+ * `target_kind` after ldt: 0 = targets uint8 [B, ldt], 1 = targets fp32 [B, ldt]; either way non-zero = positive.  logit_scale may
+ * be NULL (scale 1; dscale must then be NULL); dz bf16 [B, ldd] (optional; scored rows only, columns C .. ldd-1 zeros); prob fp32
+ * [B, ldp] (optional) = sigmoid(exp(ls) * z), the scores the eval path caches, accurate to the last places on the saturated side
+ * too (x = s z and exp(-|x|) are formed in fp64).  Rows [row0, row0 + nrows) over the full denominator B, so the losses of
+ * disjoint strips add up; a strip's dz / prob rows are the full call's bits.  One wave per row, the row in registers between the
+ * reductions and the gradient for C <= 1024 (wider rows read z twice); per-row partials in `workspace`
+ * (vipant_hinge_logits_workspace_bytes(nrows) = nrows * 8 bytes, all of it written before it is read), added in fp64 in a fixed
+ * order: no atomics, two runs are bit-identical.  Refused before any launch, nothing written: the shapes vipant_bce_logits
+ * refuses (C < 1 or >= 2^30, ldz / ldt / ldp / ldd < C, a row range outside [0, B)), target_kind other than 0 / 1. */
+size_t vipant_hinge_logits_workspace_bytes(int64_t nrows);
+int32_t vipant_hinge_logits(const float* z, int64_t ldz, const void* targets, int64_t ldt, int32_t target_kind, const float* logit_scale,
+                            float* loss, uint16_t* dz, int64_t ldd, float* dscale, float* prob, int64_t ldp, int64_t row0, int64_t nrows,
+                            float grad_scale, int64_t B, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
 /* Tagging targets from ragged class-id lists (the reference builds multi-hot rows of 527 as Python lists per item in the loader worker
  * and mixes them there, audioset_cls.py:400).  ids int32 [total]; offsets int32 [nsrc + 1]: row r's classes are
  * ids[offsets[r] : offsets[r+1]]; mix_index int32 [b] / mix_lambda fp32 [b] as in vipant_fbank_mix_src, or both NULL; y fp32 [b, C]:

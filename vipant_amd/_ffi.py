@@ -185,6 +185,9 @@ PROTOTYPES = {
     "vipant_bce_logits_workspace_bytes": (_sz, [_i64]),
     "vipant_bce_logits": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
     "vipant_bce_logits_soft": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
+    # multi-label hinge tagging loss (vipant_amd/csrc/hinge.hip)
+    "vipant_hinge_logits_workspace_bytes": (_sz, [_i64]),
+    "vipant_hinge_logits": (_i32, [_p, _i64, _p, _i64, _i32, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _f32, _i64, _i64, _p, _sz, _p]),
     # shared-input LayerNorm pair of the imagine-and-classify head (vipant_amd/csrc/imagine.hip)
     "vipant_layernorm_pair_fwd": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p]),
     "vipant_layernorm_pair_bwd_workspace_bytes": (_sz, [_i64, _i64]),

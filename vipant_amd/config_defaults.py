@@ -173,6 +173,9 @@ GROUPS = {
         "ce_cls": {"name": "ClassificationHead", "embed_dim": "${model.image.embed_dim}", "layers": [], "scaling": True},
         "bce": {"name": "BCELossHead", "embed_dim": "${model.audio.embed_dim}", "width": "${model.audio.width}", "layers": [],
                 "scaling": True, "bias": False},
+        # the reference ships no yaml for BCHingeLossHead (loss_more.py:145-198): the `bce` group under the head's name
+        "hinge": {"name": "BCHingeLossHead", "embed_dim": "${model.audio.embed_dim}", "width": "${model.audio.width}", "layers": [],
+                  "scaling": True, "bias": False},
         # configs/model/loss/imagine_and_classify.yaml: the tagging head with an image mirror (`running.imagine=True`)
         "imagine_and_classify": {
             "name": "ImagineAndClassifyLossHead", "lambd_ce": 1., "layers": ["${model.image.embed_dim}"], "bias": False,

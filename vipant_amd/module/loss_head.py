@@ -744,6 +744,29 @@ class BCELossHead(_ClassifierHead):
 
 
 @MORE_LOSS_HEADS_REGISTRY.register()
+class BCHingeLossHead(BCELossHead):
+    """The ranking counterpart of BCELossHead (cvap/module/decoder/loss_more.py:145-198): the same `linear` chain and temperature,
+    nn.MultiLabelMarginLoss on sigmoid(exp(logit_scale) x logits), a row's positives being the non-zero entries of its multi-hot
+    target (`convert_label`).  One launch (ops.hinge_logits: the closed form of the pair sum, include/vipant_hip.h), no index
+    matrix, no loop over the batch.  There are no soft hinge targets: `_target` binarises integer and floating-point input alike by
+    `!= 0`, so `soft_targets` (which ASMonitor switches on under mixup) is accepted and has no effect -- a mixed row's fractional
+    labels count as marks.  `infer` returns the hinge loss and caches the sigmoid scores and binary gold labels; `report`,
+    `zero_shot`, the device report and `copy_state_dict` are BCELossHead's."""
+
+    kind = "hinge"
+
+    def _target(self, x2, device):
+        x2 = torch.as_tensor(x2, device=device)
+        return (x2 if x2.dtype == torch.uint8 else (x2 != 0).to(torch.uint8)).contiguous()
+
+    def infer(self, x1, x2, *args, **kwargs):
+        loss = super().infer(x1, x2, *args, **kwargs)
+        if self.x2s[-1].is_floating_point():
+            self.x2s[-1] = (self.x2s[-1] != 0).to(self.x2s[-1].dtype)
+        return loss
+
+
+@MORE_LOSS_HEADS_REGISTRY.register()
 class ImagineAndClassifyLossHead(LossHead):
     """AudioSet tagging with an image mirror (cvap/module/decoder/loss_more.py:200-274): the audio feature is classified by the BCE
     head (`loss_bce`) and, through the audio -> vision projector `a2v` ([LayerNorm, Linear] pairs over `cfg.layers`, Identity when

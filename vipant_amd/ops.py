@@ -1735,6 +1735,31 @@ def _bce(entry, z, targets, logit_scale, C, row0, nrows, grad_scale, want_grad, 
     return loss, dz, dscale, prob
 
 
+def hinge_logits(z: torch.Tensor, targets: torch.Tensor, logit_scale: Optional[torch.Tensor], *, C: Optional[int] = None,
+                 row0: int = 0, nrows: Optional[int] = None, grad_scale: float = 1.0, want_grad: bool = True,
+                 ldd: Optional[int] = None, want_prob: bool = False):
+    """nn.MultiLabelMarginLoss()(sigmoid(exp(logit_scale) * z[:, :C]), positives) (vipant_hinge_logits; logit_scale None: scale 1)
+    -> (loss fp32 [1], dz bf16 [B, ldd] | None, dscale fp32 [1] | None, prob fp32 [B, C] | None), as bce_logits.  targets uint8 or
+    fp32 [B, C]: a row's positives are its non-zero entries (fractional values are marks, not weights)."""
+    _need(z, F32, "hinge_logits.z"); _need(targets, F32 if targets.dtype == F32 else torch.uint8, "hinge_logits.targets")
+    B = z.shape[0]
+    C = z.shape[1] if C is None else int(C)
+    assert targets.shape[0] == B and targets.shape[1] >= C, (z.shape, targets.shape)
+    nrows = B - row0 if nrows is None else int(nrows)
+    ldd = (z.shape[1] if ldd is None else int(ldd))
+    dev = z.device
+    ls = _ls_scalar(logit_scale, dev)
+    loss = torch.empty((1,), dtype=F32, device=dev)
+    dz = torch.empty((B, ldd), dtype=BF16, device=dev) if want_grad else None
+    dscale = torch.empty((1,), dtype=F32, device=dev) if (want_grad and ls is not None) else None
+    prob = torch.empty((B, C), dtype=F32, device=dev) if want_prob else None
+    ws = scratch("hinge", query("vipant_hinge_logits_workspace_bytes", nrows), dev)
+    call("vipant_hinge_logits", z.data_ptr(), z.stride(0), targets.data_ptr(), targets.stride(0), int(targets.dtype == F32), _ptr(ls),
+         loss.data_ptr(), _ptr(dz), ldd, _ptr(dscale), _ptr(prob), C, int(row0), nrows, float(grad_scale), B, C, ws.data_ptr(),
+         ws.numel(), _stream())
+    return loss, dz, dscale, prob
+
+
 def multihot_mix(ids: torch.Tensor, offsets: torch.Tensor, C: int, *, outputs: Optional[int] = None, mix=None) -> torch.Tensor:
     """Ragged class-id lists -> (soft) multi-hot targets fp32 [b, C] (vipant_multihot_mix).  ids int32 [total], offsets int32
     [nsrc + 1] (row r's classes are ids[offsets[r] : offsets[r + 1]]), b = outputs (default nsrc); mix = (index int32 [b] with values
@@ -1790,11 +1815,11 @@ def padded_classifier(w: torch.Tensor, bias: Optional[torch.Tensor], Cp: int):
 
 class ClassifierMeta:
     """What ClassifierFn needs besides its differentiable inputs: the loss ("ce": int64 labels [B]; "bce": uint8 multi-hot
-    targets [B, C]; "bce_soft": fp32 soft targets [B, C]), the class count, 1 / world for a replica's share of the gradient, and what the eval path wants back.
+    targets [B, C]; "bce_soft": fp32 soft targets [B, C]; "hinge": uint8 or fp32 marks [B, C], non-zero = positive), the class count, 1 / world for a replica's share of the gradient, and what the eval path wants back.
     `pred` / `prob` receive the arg-max columns / sigmoid scores of the last forward."""
 
     def __init__(self, kind: str, nclass: int, grad_scale: float = 1.0, want_pred: bool = False, want_prob: bool = False):
-        assert kind in ("ce", "bce", "bce_soft"), kind
+        assert kind in ("ce", "bce", "bce_soft", "hinge"), kind
         self.kind, self.nclass, self.grad_scale = kind, int(nclass), float(grad_scale)
         self.want_pred, self.want_prob = bool(want_pred), bool(want_prob)
         self.pred = self.prob = None
@@ -1809,7 +1834,8 @@ class ClassifierFn(torch.autograd.Function):
     Linear runs with its class dimension padded to a multiple of 64 (padded_classifier); the loss kernel reads the C valid
     columns and writes dz with zero pad columns, so the pad never enters the loss or a gradient.  LayerNorm, the contractions,
     the bias sums (from the weight-gradient contraction's operand tiles and the LayerNorm backward's `dx_colsum`) are the
-    library's; forward and loss gradient are one pass (vipant_softmax_ce / vipant_bce_logits), the backward is contractions."""
+    library's; forward and loss gradient are one pass (vipant_softmax_ce / vipant_bce_logits / vipant_hinge_logits), the backward is
+    contractions."""
 
     @staticmethod
     def forward(ctx, x, target, logit_scale, meta, *params):
@@ -1835,7 +1861,7 @@ class ClassifierFn(torch.autograd.Function):
                                              want_pred=meta.want_pred)
             meta.pred = pred
         else:
-            bce = bce_logits_soft if meta.kind == "bce_soft" else bce_logits
+            bce = {"bce": bce_logits, "bce_soft": bce_logits_soft, "hinge": hinge_logits}[meta.kind]
             loss, dz, dls, prob = bce(z, target, logit_scale, C=C, grad_scale=meta.grad_scale, want_grad=want, want_prob=meta.want_prob)
             meta.prob = prob
         if want:
