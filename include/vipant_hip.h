@@ -946,6 +946,45 @@ int32_t vipant_patch_embed_ln_bwd(const void* dout, int32_t dout_bf16, const flo
                                   int64_t Cw, int64_t khw, int32_t mean_channels, void* workspace, size_t workspace_bytes,
                                   void* stream);
 
+/* K1 with patchout (csrc/patch_keep.hip): the same operator over a kept subset of each clip's patches.
+ * keep int32 [b,k]: each row strictly ascending, values in [0, P), P = nrow*ncol of the rule above, 1 <= k <= P (the caller draws the
+ * lists and checks their contents; an entry outside [0, P) is never turned into an address: its token row is left unwritten).
+ * S' = k+1.  tokens fp32 [b*S',Dw]: row i*S' = cls + pos[0], row i*S'+1+m = patch(i, keep[i,m]) . w_eff^T + pos[1 + keep[i,m]];
+ * patches bf16 [b*k,kcols] = the kept rows of the im2col matrix, columns (c, ii, jj) -- or NULL: nothing is stored (no_grad, a frozen
+ * tower); w_eff bf16 [Dw,kcols] as in vipant_patch_embed_ln_fwd; out fp32 [b*S',Dw], mean / rstd fp32 [b*S'] = vipant_layernorm_fwd of
+ * tokens.  No matrix over all b*P patches is formed: the contraction reads x through the list.
+ * Refused with VIPANT_EBADSHAPE before the first launch, nothing written: everything vipant_patch_embed_ln_fwd refuses; k < 1 or
+ * k > P; keep == NULL; more than 65535 clips.  (VIPANT_EALIGN, likewise before any launch: w_eff, pos, tokens or patches not 16-byte aligned.) */
+int32_t vipant_patch_embed_keep_ln_fwd(const float* x, const float* conv_w, const float* cls, const float* pos, const float* gamma,
+                                       const float* beta, const int32_t* keep, uint16_t* w_eff, uint16_t* patches, float* tokens,
+                                       float* out, float* mean, float* rstd, int64_t b, int64_t C, int64_t T, int64_t F, int64_t Dw,
+                                       int64_t Cw, int64_t ph, int64_t pw, int64_t sh, int64_t sw, int64_t k, int32_t mean_channels,
+                                       void* stream);
+/* The contraction of the operator above alone: the patch rows of tokens (+ the gathered positional rows) and, when patches != NULL, the
+ * kept im2col rows; x fp32 [b,C,T,F], w_eff bf16 [Dw, C*ph*pw].  The class rows i*S' are not written.  Refusals as above (C*ph*pw % 64). */
+int32_t vipant_patch_keep_tokens(const float* x, const uint16_t* w_eff, const float* pos, const int32_t* keep, float* tokens,
+                                 uint16_t* patches, int64_t b, int64_t C, int64_t T, int64_t F, int64_t Dw, int64_t ph, int64_t pw,
+                                 int64_t sh, int64_t sw, int64_t k, void* stream);
+/* inv int32 [b,P]: inv[i,p] = the slot m with keep[i,m] == p, or -1 (keep rows ascending).  Refused with VIPANT_EBADSHAPE, nothing
+ * written: a NULL pointer, b <= 0, k < 1 or k > P. */
+int32_t vipant_patch_keep_inverse(const int32_t* keep, int32_t* inv, int64_t b, int64_t k, int64_t P, void* stream);
+/* backward of the token assembly with patchout: dtokens fp32 [b*(k+1),D] -> dpatches bf16 [b*k,D] (round to nearest even of the patch
+ * rows), dcls fp32 [D] = the sum over items of row i*(k+1), dpos[0] = dcls, dpos[1+p] = the sum over the items that kept p of their row
+ * -- added in ascending item order, no atomics: the same bits every run; rows 1 .. P nobody kept are written as zeros, rows beyond P
+ * are not touched.  Refused with VIPANT_EBADSHAPE, nothing written: a NULL pointer, b <= 0, k < 1 or k > P, D % 4 != 0. */
+int32_t vipant_assemble_tokens_keep_bwd(const float* dtokens, const int32_t* inv, uint16_t* dpatches, float* dcls, float* dpos, int64_t b,
+                                        int64_t k, int64_t P, int64_t D, void* stream);
+size_t vipant_patch_embed_keep_ln_bwd_workspace_bytes(int64_t b, int64_t k, int64_t Dw, int64_t kcols);
+/* vipant_patch_embed_ln_bwd with patchout: dtokens fp32 [b*(k+1),Dw], dpatches bf16 [b*k,Dw], dw_eff fp32 [Dw,kcols], inv int32 [b,P]
+ * scratch (inv is built here from keep); dconv, dcls, dpos (rows 0 .. P overwritten, rows beyond P not touched), dgamma, dbeta and dout
+ * as there.  Refused before the first launch, nothing written: VIPANT_EBADSHAPE for keep or inv NULL, b <= 0, k < 1 or k > P, Cw or
+ * khw <= 0, Dw not a multiple of 64 from 192 to 1024; VIPANT_ENOWORKSPACE for a workspace below the query above. */
+int32_t vipant_patch_embed_keep_ln_bwd(const void* dout, int32_t dout_bf16, const float* tokens, const float* mean, const float* rstd,
+                                       const float* gamma, const uint16_t* patches, const int32_t* keep, int32_t* inv, float* dtokens,
+                                       uint16_t* dpatches, float* dw_eff, float* dconv, float* dcls, float* dpos, float* dgamma,
+                                       float* dbeta, int64_t b, int64_t k, int64_t P, int64_t Dw, int64_t Cw, int64_t khw,
+                                       int32_t mean_channels, void* workspace, size_t workspace_bytes, void* stream);
+
 /* K6 / K7 -- the read-outs: ViTPostEncoder.forward (cvap/module/val.py:288-289) and GPTPostEncoder.forward (val.py:136-146) +
  * MetaHead's normalisation (clip_head.py:117-118).  (GPTPreEncoder.forward, val.py:109-122, is vipant_embed_tokens.)
  * feat fp32 [batch,E] = LN(x[b, idx_b]) . proj (proj_t = proj^T bf16 [E,D]); idx == NULL reads row 0 (cls) in place, else (the

@@ -166,6 +166,13 @@ PROTOTYPES = {
     "vipant_patch_embed_ln_fwd": (_i32, [_p] * 12 + [_i64] * 10 + [_i32, _p]),
     "vipant_patch_embed_ln_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "vipant_patch_embed_ln_bwd": (_i32, [_p, _i32] + [_p] * 13 + [_i64] * 5 + [_i32, _p, _sz, _p]),
+    # the same operator over kept patches (vipant_amd/csrc/patch_keep.hip)
+    "vipant_patch_embed_keep_ln_fwd": (_i32, [_p] * 13 + [_i64] * 11 + [_i32, _p]),
+    "vipant_patch_keep_tokens": (_i32, [_p] * 6 + [_i64] * 10 + [_p]),
+    "vipant_patch_keep_inverse": (_i32, [_p, _p, _i64, _i64, _i64, _p]),
+    "vipant_assemble_tokens_keep_bwd": (_i32, [_p] * 5 + [_i64] * 4 + [_p]),
+    "vipant_patch_embed_keep_ln_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "vipant_patch_embed_keep_ln_bwd": (_i32, [_p, _i32] + [_p] * 15 + [_i64] * 6 + [_i32, _p, _sz, _p]),
     "vipant_cls_ln_proj_l2norm_fwd": (_i32, [_p] * 12 + [_i64] * 4 + [_i32, _p]),
     "vipant_cls_ln_proj_l2norm_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "vipant_cls_ln_proj_l2norm_bwd": (_i32, [_p] * 18 + [_i64] * 4 + [_i32, _p, _sz, _p]),

@@ -36,12 +36,15 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-re
 # accumulators in the walk's epilogue, and the walk waits on its operand loads, so the packed forms have nothing to gain there.
 # label_nce.hip: as sigmoid_loss.hip (the same epilogue; new code is built without the packed forms).
 # hinge.hip: new code, built without the packed forms (its arithmetic is per-lane scalar and fp64; nothing to pack).
+# patch_keep.hip: new code, built without the packed forms (its f32x4 arithmetic is the epilogue's add of the positional row and the
+# item walk of dpos; both wait on memory).
 # (The feature belongs to the device pass; the host pass of the same command reports it as unknown and ignores it.)
 EXTRA_CFLAGS = {"gemm_nt.hip": ["-mllvm", "-disable-machine-sink", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm"],
                 "layernorm_widths.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "sigmoid_loss.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "label_nce.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-                "hinge.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                "hinge.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                "patch_keep.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 # files whose device assembly is kept beside the object (lib/obj/<name>-hip-amdgcn-amd-amdhsa-gfx950.s): kernels with hand-counted

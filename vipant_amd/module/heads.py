@@ -89,6 +89,8 @@ class MetaHead(nn.Module):
         # construction order follows the reference so a seed yields the same from-scratch initialisation
         self.encoder = build_encoder_module(cfg.encoder, **kwargs)
         self.pre_encoder = build_encoder_module(cfg.pre_encoder, **kwargs)
+        if getattr(self.pre_encoder, "patchout", None) is not None:
+            self.encoder.patchout = True        # the stack refuses `running.fp8_gemm` for such a tower (TransformerBackbone.fp8)
         self.post_encoder = build_encoder_module(cfg.post_encoder, **kwargs)
         self.pre_encoder_addon = build_encoder_module(cfg.pre_encoder_addon, **kwargs)
         self.post_encoder_addon = build_encoder_module(cfg.post_encoder_addon, **kwargs)

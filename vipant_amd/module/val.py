@@ -243,6 +243,32 @@ class ViTPreEncoder(MetaEncoder):
                                stride=self.stride, bias=False)
         self.patch_size = self.conv1.weight.shape[-2:]
         self.ln = LayerNorm(width)
+        # `+model.<head>.pre_encoder.patchout.keep=0.5` (or `.time=` / `.freq=`; the key is in no config group): training steps embed a
+        # random subset of every clip's patches (ops.PatchoutEmbedFn); evaluation and no_grad calls always see every patch
+        po = cfg.get("patchout", None) if hasattr(cfg, "get") else getattr(cfg, "patchout", None)
+        self.patchout = None
+        if po is not None:
+            po = dict(po) if isinstance(po, dict) else dict(vars(po))
+            unknown = set(po) - {"keep", "time", "freq"}
+            if unknown or not po:
+                from ..errors import VipantError
+                raise VipantError(f"ViTPreEncoder: patchout takes `keep`, or `time` / `freq`; got {sorted(po)}")
+            nrow, ncol = self.position_resolution[:2]
+            ops.draw_patchout(1, nrow, ncol, **po)          # a rule that leaves no patch is refused here, when the tower is built
+            self.patchout = po
+        self._patchout_seed = 0
+        self._patchout_generator = None
+
+    def seed_patchout(self, seed, rank=0):
+        """The module's own generator for the kept-patch lists: `seed` of the run and the replica's rank, so replicas draw different
+        lists (Monitor._configure)."""
+        self._patchout_seed = int(seed) + 4409 + 1000 * max(int(rank), 0)
+        self._patchout_generator = None
+
+    def draw_keep(self, b, nrow, ncol):
+        if self._patchout_generator is None:
+            self._patchout_generator = torch.Generator().manual_seed(self._patchout_seed)
+        return ops.draw_patchout(b, nrow, ncol, generator=self._patchout_generator, **self.patchout)
 
     def initialize_parameters(self):
         pass
@@ -265,12 +291,20 @@ class ViTPreEncoder(MetaEncoder):
     def dtype(self):
         return self.conv1.weight.dtype
 
-    def forward(self, x, positional_embedding=None, class_embedding=None, **kwargs):
+    def forward(self, x, positional_embedding=None, class_embedding=None, keep=None, **kwargs):
+        """`keep` (int32 [b, k], ops.draw_patchout): an explicit list of kept patches for a patchout step (tests); None: drawn."""
         assert x.dim() == 4, f"expect 4d `x` but get x.dim == {x.dim()}"
         w = self.conv1.weight
         if x.shape[1] != 3:
             w = interp_conv_weight_spatial(w, self.patch_size)       # no-op unless the kernel was re-gridded
         b = x.shape[0]
+        if self.patchout is not None and self.training and torch.is_grad_enabled():
+            if keep is None:
+                ph, pw = w.shape[-2:]
+                keep = self.draw_keep(b, (x.shape[2] - ph) // self.stride[0] + 1, (x.shape[3] - pw) // self.stride[1] + 1)
+            out = ops.PatchoutEmbedFn.apply(x.to(torch.float32), w, class_embedding, positional_embedding,
+                                            self.ln.weight, self.ln.bias, tuple(self.stride), keep)
+            return out.view(b, -1, out.shape[-1])
         out = ops.PatchEmbedFn.apply(x.to(torch.float32), w, class_embedding, positional_embedding,
                                      self.ln.weight, self.ln.bias, tuple(self.stride))
         return out.view(b, -1, out.shape[-1])
@@ -363,6 +397,10 @@ class TransformerBackbone(MetaEncoder):
             from ..errors import VipantError
             raise VipantError(f"running.fp8_gemm=True: a tower of width {self.width} has no e4m3 kernels; the widths with e4m3 towers "
                               "are 256, 512, 768 and 1024")
+        if on and getattr(self, "patchout", False):       # MetaHead marks the stack of a tower whose pre-encoder has `patchout`
+            from ..errors import VipantError
+            raise VipantError("running.fp8_gemm=True: a tower with `pre_encoder.patchout` is refused: e4m3 plans over the kept "
+                              "rows are not supported; drop one of the two keys")
         self._fp8 = bool(on)
 
     def build_attention_mask(self):

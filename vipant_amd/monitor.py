@@ -186,6 +186,9 @@ class Monitor(object):
         # `running.last_block_rows` (default on): a tower's last block is evaluated on the rows its read-out takes (class / end-of-text
         # token) -- exact, see ops.BackboneFn; off: the full block, as the reference computes it before discarding the other rows
         last_rows = bool(cfg.running.get("last_block_rows", True)) and os.environ.get("VIPANT_LAST_BLOCK_ROWS", "1") != "0"
+        for head in towers:      # `pre_encoder.patchout`: the lists come from the run's seed and the rank, replicas draw different ones
+            if head is not None and hasattr(getattr(head, "pre_encoder", None), "seed_patchout"):
+                head.pre_encoder.seed_patchout(int(cfg.seed), max(int(cfg.rank), 0))
         for head in towers:
             if head is not None and hasattr(head, "encoder"):
                 head.encoder.stream_f16 = stream_f16

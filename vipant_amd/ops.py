@@ -548,6 +548,124 @@ class PatchEmbedFn(torch.autograd.Function):
         return None, dconv, dcls, dpos, dlnw, dlnb, None
 
 
+def draw_patchout(b: int, nrow: int, ncol: int, *, keep=None, time: int = 0, freq: int = 0,
+                  generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """The kept patches of one batch, drawn on the host -> int32 [b, k], every row strictly ascending, values in [0, nrow * ncol)
+    (patch = grid row * ncol + grid column).  Unstructured: `keep` is a count (int) or a fraction in (0, 1] (float; rounded down, at
+    least 1); every clip gets its own uniform k-subset (the k smallest of nrow * ncol uniform draws).  Structured: every clip drops
+    `time` grid rows and `freq` grid columns of its own (the smallest of nrow + ncol uniform draws), k = (nrow - time) (ncol - freq).
+    The two forms exclude each other.  Every clip consumes the same number of draws."""
+    P = int(nrow) * int(ncol)
+    if b <= 0 or nrow <= 0 or ncol <= 0:
+        raise _ffi.VipantError(f"draw_patchout: need b, nrow, ncol > 0 (b={b}, grid {nrow} x {ncol})")
+    if keep is not None:
+        if time or freq:
+            raise _ffi.VipantError("draw_patchout: `keep` (unstructured) and `time` / `freq` (structured) exclude each other")
+        if isinstance(keep, float):
+            if not 0.0 < keep <= 1.0:
+                raise _ffi.VipantError(f"draw_patchout: a kept fraction lies in (0, 1], got {keep}")
+            k = max(int(keep * P), 1)
+        else:
+            k = int(keep)
+        if not 1 <= k <= P:
+            raise _ffi.VipantError(f"draw_patchout: keep={keep} leaves {k} of {P} patches, need 1 .. {P}")
+        u = torch.rand(b, P, generator=generator, dtype=torch.float64)
+        return u.argsort(dim=1)[:, :k].sort(dim=1).values.to(torch.int32)
+    time, freq = int(time), int(freq)
+    if time < 0 or freq < 0 or time >= nrow or freq >= ncol:
+        raise _ffi.VipantError(f"draw_patchout: dropping {time} rows and {freq} columns of a {nrow} x {ncol} grid leaves no patch")
+    u = torch.rand(b, nrow + ncol, generator=generator, dtype=torch.float64)
+    rows = u[:, :nrow].argsort(dim=1)[:, time:].sort(dim=1).values          # the grid rows a clip keeps, ascending
+    cols = u[:, nrow:].argsort(dim=1)[:, freq:].sort(dim=1).values
+    return (rows.unsqueeze(2) * ncol + cols.unsqueeze(1)).reshape(b, -1).to(torch.int32)
+
+
+class PatchoutEmbedFn(torch.autograd.Function):
+    """PatchEmbedFn over the kept patches of every clip (patchout; csrc/patch_keep.hip, vipant_patch_embed_keep_ln_{fwd,bwd}): x fp32
+    [b, C, T, F], keep int32 [b, k] (ops.draw_patchout; host or device) -> residual stream fp32 [b * (k + 1), D].  No im2col matrix over
+    all patches, no gather in torch: the contraction reads x through the list.  The stream-gradient hand-over is PatchEmbedFn's."""
+
+    @staticmethod
+    def forward(ctx, x, conv_w, cls, pos, ln_w, ln_b, stride, keep):
+        _need(x, F32, "patchout_embed.x")
+        x = x.contiguous()
+        b, Cx, T, Fq = x.shape
+        D, Cw, ph, pw = conv_w.shape
+        sh, sw = int(stride[0]), int(stride[1])
+        if min(b, sh, sw, ph, pw) <= 0 or T < ph or Fq < pw:
+            raise _ffi.VipantError(f"patchout_embed: input {tuple(x.shape)}, kernel {ph} x {pw}, stride {sh} x {sw}: every extent and stride "
+                                   "must be positive and the input at least one patch large")
+        if Cx != 3 and Cx != Cw and Cx != 1:
+            raise _ffi.VipantError(f"patchout_embed: the input has {Cx} channels, the kernel {Cw}: only a 3-channel, a {Cw}-channel or a "
+                                   "1-channel input (channel-mean kernel) is defined")
+        nrow, ncol = (T - ph) // sh + 1, (Fq - pw) // sw + 1
+        P = nrow * ncol
+        assert pos.shape[0] >= P + 1, f"positional table has {pos.shape[0]} rows, need {P + 1}"
+        mean_ch = Cx != 3 and Cx != Cw
+        assert mean_ch or Cx == Cw, f"input has {Cx} channels, kernel {Cw}"
+        # the list's contents are checked here, on the host, where it was drawn (the kernels take them as given)
+        if keep.dtype != torch.int32 or keep.dim() != 2 or keep.shape[0] != b:
+            raise _ffi.VipantError(f"patchout_embed: keep must be int32 [b, k] with b = {b}, got {keep.dtype} {tuple(keep.shape)}")
+        k = int(keep.shape[1])
+        if not keep.is_cuda:
+            if k < 1 or k > P or int(keep.min()) < 0 or int(keep.max()) >= P or (k > 1 and bool((keep[:, 1:] <= keep[:, :-1]).any())):
+                raise _ffi.VipantError(f"patchout_embed: every row of keep must ascend strictly inside [0, {P}) with 1 <= k <= {P} (k={k})")
+        elif k < 1 or k > P:
+            raise _ffi.VipantError(f"patchout_embed: need 1 <= k <= {P} (k={k})")
+        dev = x.device
+        keep = keep.to(dev).contiguous()
+        kcols = (1 if mean_ch else Cw) * ph * pw
+        S1 = k + 1
+        train = any(ctx.needs_input_grad)
+        w_eff = torch.empty((D, kcols), dtype=BF16, device=dev)
+        patches = torch.empty((b * k, kcols), dtype=BF16, device=dev) if train else None
+        tok = torch.empty((b * S1, D), dtype=F32, device=dev)
+        out = torch.empty((b * S1, D), dtype=F32, device=dev)
+        mean, rstd = _stats(b * S1, dev)
+        call("vipant_patch_embed_keep_ln_fwd", x.data_ptr(), conv_w.detach().contiguous().data_ptr(),
+             cls.detach().contiguous().data_ptr(), pos.detach().contiguous().data_ptr(), ln_w.detach().data_ptr(),
+             ln_b.detach().data_ptr(), keep.data_ptr(), w_eff.data_ptr(), _ptr(patches), tok.data_ptr(), out.data_ptr(),
+             mean.data_ptr(), rstd.data_ptr(), b, Cx, T, Fq, D, Cw, ph, pw, sh, sw, k, int(mean_ch), _stream())
+        if train:
+            ctx.save_for_backward(patches, tok, mean, rstd, ln_w, keep)
+        ctx.meta = (b, k, P, D, Cw, ph * pw, mean_ch, tuple(conv_w.shape), tuple(pos.shape))
+        ctx._vipant_kind = "patch"
+        ctx.stream_grad = None          # the stack's bf16 stream gradient, handed over by BackboneFn.backward
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        patches, tok, mean, rstd, ln_w, keep = ctx.saved_tensors
+        b, k, P, D, Cw, khw, mean_ch, conv_shape, pos_shape = ctx.meta
+        dev = dout.device
+        handed, ctx.stream_grad = ctx.stream_grad, None
+        dout_bf16 = handed is not None and _is_placeholder(dout, handed[1])
+        if dout_bf16:
+            dout = handed[0]
+        else:
+            dout = dout.contiguous()
+            if handed is not None:      # another consumer of the stream contributed a real gradient: add the stack's to it
+                dout = dout + handed[0].to(F32)
+        kcols = patches.shape[1]
+        inv = torch.empty((b, P), dtype=torch.int32, device=dev)
+        dtok = torch.empty_like(tok)
+        dpatch = torch.empty((b * k, D), dtype=BF16, device=dev)
+        dw_eff = torch.empty((D, kcols), dtype=F32, device=dev)
+        dconv = torch.empty(conv_shape, dtype=F32, device=dev) if mean_ch else dw_eff.view(conv_shape)
+        dcls = torch.empty((D,), dtype=F32, device=dev)
+        dpos = torch.empty(pos_shape, dtype=F32, device=dev)      # rows 0 .. P are written by the kernel (zeros where nobody kept)
+        if pos_shape[0] > P + 1:
+            dpos[P + 1:].zero_()
+        dlnw = torch.empty((D,), dtype=F32, device=dev)
+        dlnb = torch.empty((D,), dtype=F32, device=dev)
+        ws = scratch("patch_embed_bwd", query("vipant_patch_embed_keep_ln_bwd_workspace_bytes", b, k, D, kcols), dev)
+        call("vipant_patch_embed_keep_ln_bwd", dout.data_ptr(), int(dout_bf16), tok.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+             ln_w.detach().data_ptr(), patches.data_ptr(), keep.data_ptr(), inv.data_ptr(), dtok.data_ptr(), dpatch.data_ptr(),
+             dw_eff.data_ptr(), dconv.data_ptr(), dcls.data_ptr(), dpos.data_ptr(), dlnw.data_ptr(), dlnb.data_ptr(), b, k, P, D, Cw,
+             khw, int(mean_ch), ws.data_ptr(), ws.numel(), _stream())
+        return None, dconv, dcls, dpos, dlnw, dlnb, None, None
+
+
 # ---------------------------------------------------------------------------------- transformer
 class _LayerGrads:
     """fp32 gradients of one block, carved from one flat buffer so a replica group can all-reduce a whole
