@@ -736,6 +736,34 @@ int32_t vipant_adam_step(float* const* p, const float* const* g, float* const* m
                          const float* rec, const int32_t* chunk_start, int64_t ntensors, int64_t nchunks, int64_t chunk,
                          double beta1, double beta2, int32_t decoupled, void* stream);
 
+/* ---- LAMB with global gradient-norm clipping (You et al., ICLR 2020, Alg. 2; `optimizer: [LAMB, {...}]`), one launch group per
+ * tensor list ------------------------------------------------------------------------------------------------------------------
+ * Tables as vipant_adam_step takes them (p / g / m / v device arrays of device pointers, n, chunk_start, nchunks, chunk: the same
+ * split, vipant_adam_chunk_elements() is the size to use).  rec[8 i .. 8 i + 7] = {lr, 1 / bc1, 1 / sqrt(bc2), eps, wd, adapt, 0, 0}
+ * with bc1 = 1 - beta1^step, bc2 = 1 - beta2^step, adapt = 0 or 1, computed in doubles and rounded once to fp32; 16-byte aligned.
+ *   G  = sqrt(sum over every tensor of the call of sum g^2);   c = max_grad_norm > 0 ? min(1, max_grad_norm / (G + 1e-6)) : 1
+ *   g' = c * g;   m = m + (1 - beta1) * (g' - m);   v = beta2 * v + (1 - beta2) * g' * g'
+ *   u  = (m * rec[1]) / (sqrt(v) * rec[2] + eps) + wd * p;   phi = adapt && |p|_2 > 0 && |u|_2 > 0 ? |p|_2 / |u|_2 : 1  (whole tensor)
+ *   p  = p - (lr * phi) * u
+ * Gradients are read only; u is recomputed by the last pass, never stored.  Launches: sum g^2 per chunk and its fold (both skipped
+ * when max_grad_norm == 0), the moments with sum p^2 / sum u^2 per chunk, one fold per tensor, the update: 40 B per element, 44 with
+ * the clip.  Per-chunk sums are fp32 (fixed tree), folded in fp64 in ascending chunk order; no float atomics, no host round trip,
+ * nothing allocated: the same bits on every run, whatever the workspace held.  A non-finite G is used as computed.
+ * workspace (vipant_lamb_workspace_bytes, 16-byte aligned), in floats: {G, c, -, -}, phi[ntensors], then sum g^2, sum p^2, sum u^2
+ * [nchunks] each, every section rounded up to four floats; G and c are written only when max_grad_norm > 0.
+ * Refused before any launch, nothing written: what vipant_adam_step refuses and a negative max_grad_norm (VIPANT_EBADSHAPE), a NULL,
+ * misaligned or too small workspace (VIPANT_ENOWORKSPACE). */
+size_t vipant_lamb_workspace_bytes(int64_t ntensors, int64_t nchunks);
+int32_t vipant_lamb_step(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
+                         const float* rec, const int32_t* chunk_start, int64_t ntensors, int64_t nchunks, int64_t chunk,
+                         double beta1, double beta2, double max_grad_norm, void* workspace, size_t workspace_bytes, void* stream);
+/* The first two launches of the group on their own: out[0] (device, fp32) = G over the list g / n / chunk_start -- the same partial
+ * sums and the same fold, hence the same bits of G as a vipant_lamb_step over the same list and chunk size.  workspace
+ * (vipant_grad_norm_workspace_bytes, 16-byte aligned), in floats: {G, 1, -, -}, sum g^2 [nchunks].  Refusals as above. */
+size_t vipant_grad_norm_workspace_bytes(int64_t nchunks);
+int32_t vipant_grad_norm(const float* const* g, const int64_t* n, const int32_t* chunk_start, int64_t ntensors, int64_t nchunks,
+                         int64_t chunk, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Barlow Twins loss head (BarlowLossHead, cvap/module/decoder/loss_head.py:287-328) -----------------------------------
  * Batch normalisation over the batch dimension (torch.nn.BatchNorm1d, training mode, loss_head.py:296-303, 313): x fp32 [M, N]
  * (row stride ldx) -> y bf16 [M, N] (row stride N) = [ReLU]((x - mean) * rstd [* gamma + beta]); mean / rstd fp32 [N] are the

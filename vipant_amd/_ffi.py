@@ -180,6 +180,11 @@ PROTOTYPES = {
     "vipant_lars_step": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _f32, _f32, _f32, _p, _sz, _p]),
     "vipant_adam_chunk_elements": (_i64, []),
     "vipant_adam_step": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f64, _f64, _i32, _p]),
+    # LAMB with global gradient-norm clipping (vipant_amd/csrc/lamb.hip)
+    "vipant_lamb_workspace_bytes": (_sz, [_i64, _i64]),
+    "vipant_lamb_step": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f64, _f64, _f64, _p, _sz, _p]),
+    "vipant_grad_norm_workspace_bytes": (_sz, [_i64]),
+    "vipant_grad_norm": (_i32, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _sz, _p]),
     # Barlow Twins loss head (vipant_amd/csrc/barlow.hip)
     "vipant_batchnorm_workspace_bytes": (_sz, [_i64, _i64]),
     "vipant_batchnorm_fwd": (_i32, [_p, _i64, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _f32, _f32, _i64, _i64, _p, _sz, _p]),

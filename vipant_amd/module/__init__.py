@@ -6,6 +6,7 @@ from .val import (  # noqa: F401
 )
 from .lars import *  # noqa: F401,F403
 from .adam import *  # noqa: F401,F403
+from .lamb import *  # noqa: F401,F403
 from .heads import (  # noqa: F401
     IMAGE_HEADS_REGISTRY, AUDIO_HEADS_REGISTRY, TEXT_HEADS_REGISTRY, build_image_head, build_audio_head,
     build_text_head, MetaHead, CLIPImageHead, CLIPAudioHead, CLIPTextHead, DummyHead, position_resolution,

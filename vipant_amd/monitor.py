@@ -34,7 +34,7 @@ from ._ffi import VipantError
 from .audio_batch import FBANK_NORMS, PRIME_MASKS, SECOND_MASKS, AudioBatches
 from .data import FrameBatch, LogmelBatch, PcmBatch, RawPcmBatch, SecondView
 from .model import build_main_model
-from .module import LARS, Adam, AdamW, adjust_learning_rate, exclude_bias_or_norm
+from .module import LAMB, LARS, Adam, AdamW, adjust_learning_rate, exclude_bias_or_norm
 
 SOT, EOT = 49406, 49407
 
@@ -645,9 +645,15 @@ class Monitor(object):
             # classes that override `step()` only -- one vipant_adam_step launch; `+optimizer.fused_step=False` restores torch's
             # own classes); any other name runs through torch's optimizer kernels.  Forward / backward are the HIP path either way.
             ocfg_opt, ocfg_sch = ocfg.optimizer, ocfg.scheduler
-            fused = {"Adam": Adam, "AdamW": AdamW} if bool(ocfg.get("fused_step", True)) else {}
-            optimizer_cls = fused.get(ocfg_opt[0]) or getattr(torch.optim, ocfg_opt[0])
-            self.optimizer = optimizer_cls(param_groups, **dict(ocfg_opt[1]))
+            # LAMB (module/lamb.py; torch ships none) steps through vipant_lamb_step, or through the class's plain torch step with
+            # `+optimizer.fused_step=False`.
+            fused_step = bool(ocfg.get("fused_step", True))
+            fused = {"Adam": Adam, "AdamW": AdamW} if fused_step else {}
+            if ocfg_opt[0] == "LAMB":
+                self.optimizer = LAMB(param_groups, fused=fused_step, **dict(ocfg_opt[1]))
+            else:
+                optimizer_cls = fused.get(ocfg_opt[0]) or getattr(torch.optim, ocfg_opt[0])
+                self.optimizer = optimizer_cls(param_groups, **dict(ocfg_opt[1]))
             self.scheduler = getattr(torch.optim.lr_scheduler, ocfg_sch[0])(self.optimizer, **dict(ocfg_sch[1]))
         if self.cfg.verbose:
             self.echo("Gradienting The Following Parameters:")

@@ -1631,6 +1631,113 @@ class AdamState:
              int(bool(decoupled)), _stream())
 
 
+class LambState:
+    """Device-side tables for vipant_lamb_step (LAMB with global gradient-norm clipping, csrc/lamb.hip), built once per parameter
+    list as AdamState builds its own: pointers of p / exp_avg / exp_avg_sq, element counts, the prefix table of chunk counts (the same
+    chunk size), and the workspace of the launch group -- the caller's (`workspace`, uint8, at least `workspace_bytes()`, 16-byte
+    aligned) or one allocated here.  The moments are the caller's tensors: the kernels write them in place.
+
+    Per step, the per-tensor record {lr, 1 / bc1, 1 / sqrt(bc2), eps, wd, adapt, 0, 0} (fp32, rounded once from doubles) and the
+    gradient pointers reach the device through `_PinnedStage`.  `grad_norm` / `clip_coef` are views of the workspace: G and c of the
+    last step that clipped, on the device."""
+
+    def __init__(self, params: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor], exp_avg_sqs: Sequence[torch.Tensor],
+                 workspace: Optional[torch.Tensor] = None):
+        self.params, self.m, self.v = list(params), list(exp_avgs), list(exp_avg_sqs)
+        dev = self.params[0].device
+        n = len(self.params)
+        for p, m, v in zip(self.params, self.m, self.v):
+            for x in (p, m, v):
+                assert x.is_contiguous() and x.dtype == F32 and x.device == dev and x.shape == p.shape
+        self.chunk = AdamState.chunk_elements()
+        self.n, self.chunk_start, self.nchunks = _chunk_tables([p.numel() for p in self.params], self.chunk, dev)
+        self.p_ptrs = _to_device([p.data_ptr() for p in self.params], I64, dev)
+        self.m_ptrs = _to_device([m.data_ptr() for m in self.m], I64, dev)
+        self.v_ptrs = _to_device([v.data_ptr() for v in self.v], I64, dev)
+        need = self.workspace_bytes(n, self.nchunks)
+        if workspace is None:
+            workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+        assert workspace.dtype == torch.uint8 and workspace.device == dev and workspace.is_contiguous() and workspace.numel() >= need
+        self.ws = workspace
+        # records first (n x 8 fp32: 16-byte aligned), then the gradient pointers (n x int64): one host-to-device copy per step
+        self._stage = _PinnedStage(40 * n, dev)
+        self.rec = self._stage.dev[:32 * n].view(F32)
+        self.g_ptrs = self._stage.dev[32 * n:].view(I64)
+
+    @staticmethod
+    def workspace_bytes(ntensors: int, nchunks: int) -> int:
+        return query("vipant_lamb_workspace_bytes", ntensors, nchunks)
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        return self.ws[:4].view(F32)[0]
+
+    @property
+    def clip_coef(self) -> torch.Tensor:
+        return self.ws[4:8].view(F32)[0]
+
+    @staticmethod
+    def record(lr: float, weight_decay: float, eps: float, beta1: float, beta2: float, step: float, adapt: bool):
+        """The per-tensor record of vipant_lamb_step in Python doubles."""
+        bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
+        return (lr, 1.0 / bc1, 1.0 / bc2 ** 0.5, eps, weight_decay, 1.0 if adapt else 0.0, 0.0, 0.0)
+
+    def step(self, grads: Sequence[torch.Tensor], records: Sequence[Tuple[float, ...]], beta1: float, beta2: float,
+             max_grad_norm: float = 0.0, checked: bool = False):
+        """`checked`: the caller has verified what the loop below asserts (the kernels read n[i] floats behind every pointer)."""
+        if not checked:
+            for p, g in zip(self.params, grads):
+                assert g.is_contiguous() and g.dtype == F32 and g.shape == p.shape and g.device == p.device
+        n = len(self.params)
+        assert len(grads) == n and len(records) == n
+        if self.nchunks == 0:            # nothing but empty tensors
+            return
+        hb = self._stage.host()
+        hb[:32 * n].view(F32).copy_(torch.tensor(records, dtype=torch.float64).reshape(-1))        # the one rounding to fp32
+        hb[32 * n:].view(I64).copy_(torch.tensor([g.data_ptr() for g in grads], dtype=I64))
+        self._stage.push()
+        call("vipant_lamb_step", self.p_ptrs.data_ptr(), self.g_ptrs.data_ptr(), self.m_ptrs.data_ptr(), self.v_ptrs.data_ptr(),
+             self.n.data_ptr(), self.rec.data_ptr(), self.chunk_start.data_ptr(), n, self.nchunks, self.chunk, float(beta1), float(beta2),
+             float(max_grad_norm), self.ws.data_ptr(), self.ws.numel(), _stream())
+
+
+def _chunk_tables(numels: Sequence[int], chunk: int, dev: torch.device):
+    """(n int64 [T], chunk_start int32 [T + 1], nchunks) on `dev`, through pinned memory and stream-ordered copies: no synchronisation."""
+    starts = [0]
+    for k in numels:
+        starts.append(starts[-1] + (k + chunk - 1) // chunk)
+    return _to_device(list(numels), I64, dev), _to_device(starts, torch.int32, dev), starts[-1]
+
+
+def _to_device(values, dtype, dev: torch.device) -> torch.Tensor:
+    host = torch.tensor(values, dtype=dtype)
+    if dev.type != "cuda":
+        return host.to(dev)
+    return host.pin_memory().to(dev, non_blocking=True)       # (the pinned block returns to torch's host cache behind the copy)
+
+
+def grad_norm(tensors: Sequence[torch.Tensor]) -> torch.Tensor:
+    """The 2-norm of all `tensors` together (fp32, contiguous, on one device) as a 0-d fp32 device tensor: vipant_grad_norm, the first
+    two launches of the LAMB step, hence the very G that step clips by.  Nothing here waits for the stream."""
+    ts = [t for t in tensors if t.numel()]
+    if not ts:
+        raise _ffi.VipantError("grad_norm: no elements")
+    dev = ts[0].device
+    for t in ts:
+        if not t.is_cuda:
+            raise _ffi.VipantError("grad_norm: expected device tensors (the HIP path has no CPU fallback)")
+        if t.dtype != F32 or t.device != dev or not t.is_contiguous():
+            raise _ffi.VipantError("grad_norm: the tensors must be fp32, contiguous and on one device")
+    chunk = AdamState.chunk_elements()
+    n, chunk_start, nchunks = _chunk_tables([t.numel() for t in ts], chunk, dev)
+    ptrs = _to_device([t.data_ptr() for t in ts], I64, dev)
+    ws = torch.empty((query("vipant_grad_norm_workspace_bytes", nchunks),), dtype=torch.uint8, device=dev)
+    out = torch.empty((), dtype=F32, device=dev)
+    call("vipant_grad_norm", ptrs.data_ptr(), n.data_ptr(), chunk_start.data_ptr(), len(ts), nchunks, chunk, out.data_ptr(), ws.data_ptr(),
+         ws.numel(), _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------- Barlow Twins head
 def batchnorm_fwd(x: torch.Tensor, gamma=None, beta=None, *, relu: bool = False, running_mean=None, running_var=None,
                   num_batches_tracked=None, momentum: float = 0.1, eps: float = 1e-5):
