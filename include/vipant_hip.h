@@ -421,6 +421,33 @@ int32_t vipant_label_nce_fwd_bwd(const float* x1, const float* x2, const int32_t
                                  float* loss, float* dx1, float* dx2, float* dlogit_scale, float grad_scale, int64_t B, int64_t E,
                                  int64_t row0, int64_t nrows, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Similarity-weighted InfoNCE: a frozen teacher's pairwise similarity spreads the soft-max target (SoftCELossHead) ------
+ * x1, x2 fp32 [B, E] (L2-normalised); t fp32 [B, Et] (L2-normalised teacher rows, constant: no gradient flows into it; it may alias
+ * x1 or x2; NULL: W = I, Et is ignored); logit_scale: DEVICE scalar, the raw parameter.
+ *   s = min(exp(logit_scale), scale_max) (scale_max <= 0: no clamp);  z_ij = s <x1_i, x2_j>;  c_ij = <t_i, t_j>;
+ *   W_ii = 1;  W_ij = clamp((c_ij - w_floor) / (1 - w_floor), 0, 1) ^ w_power (i != j);  n_i = sum_j W_ij (W is symmetric: row and
+ *   column sums agree up to fp32 rounding);  w_floor = -1, w_power = 1 is CWCL's (1 + c) / 2;
+ *   loss = (1/B) sum_i [ lse_j z_ij - (1/n_i) sum_j W_ij z_ij ] + (1/B) sum_j [ lse_i z_ij - (1/n_j) sum_i W_ij z_ij ];
+ *   G_ij = ( exp(z_ij - rlse_i) + exp(z_ij - clse_j) - W_ij (1/n_i + 1/n_j) ) / B;  dx1 = s G x2;  dx2 = s G^T x1;
+ *   dlogit_scale = sum_ij G_ij z_ij (0 where the clamp is active).  With t == NULL this is vipant_infonce_fwd_bwd's loss; with
+ *   bit-identical teacher rows inside groups and w_floor just under 1 it is vipant_label_nce_fwd_bwd's.
+ * STRIP CONVENTION (vipant_label_nce_fwd_bwd's): loss and dlogit_scale are the full-batch values on every caller; dx1, dx2 fp32
+ * [nrows, E] are the rows [row0, row0 + nrows); dx1, dx2 and dlogit_scale are scaled by grad_scale.  dlogit_scale is written
+ * whenever it is non-NULL; NULL dx1 / dx2 are not computed, and with both NULL or nrows == 0 there is no gradient walk.
+ * Two walks of the pair matrix at every B (statistics over the batch, gradients over the strip), each forming BOTH products per tile
+ * at fp32 grade (bf16 hi/lo split on MFMA, operands of both sides staged through LDS by 64-row workgroups), G as a bf16 MFMA operand
+ * held in registers, nothing B x B or nrows x B stored; workspace = bf16 operand copies (12 B E + 4 B Et bytes) + 12 bytes per row.
+ * Deterministic (no atomics, every sum in a fixed order).
+ * 1 <= B <= 2^19, E % 64 == 0, 64 <= E <= 1024, the same range for Et when t is given, -1 <= w_floor < 1, w_power > 0, 0 <= nrows,
+ * 0 <= row0, row0 + nrows <= B; anything else is refused before any launch, writing nothing (VIPANT_EBADSHAPE / VIPANT_ENOWORKSPACE
+ * for a NULL or short workspace / VIPANT_EALIGN: workspace 256-byte, dx1 / dx2 16-byte aligned).  The workspace query (Et == 0: no
+ * teacher) returns 0 for a shape the call refuses.  No allocation and no synchronisation in the call. */
+size_t vipant_soft_nce_workspace_bytes(int64_t B, int64_t E, int64_t Et, int64_t nrows);
+int32_t vipant_soft_nce_fwd_bwd(const float* x1, const float* x2, const float* t, int64_t Et, float w_floor, float w_power,
+                                const float* logit_scale, float scale_max, float* loss, float* dx1, float* dx2, float* dlogit_scale,
+                                float grad_scale, int64_t B, int64_t E, int64_t row0, int64_t nrows, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* ---- Retrieval evaluation (LossHead.report / retrieval_eval, cvap/module/decoder/loss_head.py:71-168) ----
  * x1 fp32 [N1, E] queries, x2 fp32 [N2, E] candidates (both L2-normalised by the caller), gold int32 [N1, G]
  * with entries in [0, N2).  Replaces `(x1 @ x2.t()).argsort(descending=True)` + `torch.where(ind == label)`:

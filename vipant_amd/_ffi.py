@@ -132,6 +132,8 @@ PROTOTYPES = {
     "vipant_sigmoid_loss_fwd_bwd": (_i32, [_p, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _f32, _i64, _i64, _i64, _i64, _p, _sz, _p]),
     "vipant_label_nce_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "vipant_label_nce_fwd_bwd": (_i32, [_p, _p, _p, _p, _f32, _p, _p, _p, _p, _f32, _i64, _i64, _i64, _i64, _p, _sz, _p]),
+    "vipant_soft_nce_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "vipant_soft_nce_fwd_bwd": (_i32, [_p, _p, _p, _i64, _f32, _f32, _p, _f32, _p, _p, _p, _p, _f32, _i64, _i64, _i64, _i64, _p, _sz, _p]),
     "vipant_retrieval_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "vipant_retrieval_ranks": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _sz, _p]),
     "vipant_tagging_stats_workspace_bytes": (_sz, [_i64, _i64]),

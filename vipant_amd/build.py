@@ -35,6 +35,7 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-re
 # sigmoid_loss.hip: the same choice, not measured against the packed form: its only f32x4 arithmetic is the sum and scaling of the
 # accumulators in the walk's epilogue, and the walk waits on its operand loads, so the packed forms have nothing to gain there.
 # label_nce.hip: as sigmoid_loss.hip (the same epilogue; new code is built without the packed forms).
+# soft_nce.hip: as label_nce.hip (its f32x4 arithmetic is the scaling of the accumulators in the gradient walk's epilogue).
 # hinge.hip: new code, built without the packed forms (its arithmetic is per-lane scalar and fp64; nothing to pack).
 # patch_keep.hip: new code, built without the packed forms (its f32x4 arithmetic is the epilogue's add of the positional row and the
 # item walk of dpos; both wait on memory).
@@ -45,6 +46,7 @@ EXTRA_CFLAGS = {"gemm_nt.hip": ["-mllvm", "-disable-machine-sink", "-mllvm", "-a
                 "layernorm_widths.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "sigmoid_loss.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "label_nce.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                "soft_nce.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "hinge.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "patch_keep.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "lamb.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}

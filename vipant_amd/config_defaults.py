@@ -159,6 +159,12 @@ GROUPS = {
         "ce_label": {"name": "LabelCELossHead", "layers": [], "scaling": True, "scale_max": None},
         "ce_val_label": {"name": "VALCELossHead", "layers": [], "scaling": True, "scale_max": None,
                          "va": True, "lv": False, "al": True, "label_positives": ["al"]},
+        # similarity-weighted InfoNCE (CWCL): the frozen side's own pairwise similarity spreads the soft-max target over the batch
+        # (SoftCELossHead; teacher: x2 | x1 | given); ce_val_soft: the image teaches the VA pair, the text the AL pair
+        "ce_soft": {"name": "SoftCELossHead", "layers": [], "scaling": True, "scale_max": None, "teacher": "x2", "w_floor": -1.0,
+                    "w_power": 1.0},
+        "ce_val_soft": {"name": "VALCELossHead", "layers": [], "scaling": True, "scale_max": None, "va": True, "lv": False, "al": True,
+                        "w_floor": -1.0, "w_power": 1.0, "soft_positives": {"va": "x1", "al": "x2"}},
         # configs/model/loss/ce_va.yaml: v = image view 1, p = the precomputed ("prime") image features, a = audio
         "ce_va": {"name": "VACELossHead", "layers": [], "scaling": True, "scale_max": None,
                   "vp": True, "vp_w": 1., "ap": False, "ap_w": 1., "va": True, "va_w": 1., "vv": True, "vv_w": 1.,

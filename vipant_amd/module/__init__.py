@@ -14,7 +14,7 @@ from .heads import (  # noqa: F401
 )
 from .loss_head import (  # noqa: F401
     LOSS_HEADS_REGISTRY, MORE_LOSS_HEADS_REGISTRY, build_loss_head, LossHead, CELossHead, VALCELossHead, BarlowLossHead, BarlowCELossHead, DummyLossHead,
-    ClassificationHead, BCELossHead, BCHingeLossHead, ImagineAndClassifyLossHead, LabelCELossHead, zero_shot_report,
+    ClassificationHead, BCELossHead, BCHingeLossHead, ImagineAndClassifyLossHead, LabelCELossHead, SoftCELossHead, zero_shot_report,
 )
 
 LOSS_HEADS_REGISTRY._do_register("DummyHead", DummyLossHead)

@@ -287,11 +287,61 @@ class LabelCELossHead(CELossHead):
         return ops.LabelNCEFn.apply(x1, x2, groups, ls, scale_max, 0, b, 1.0 / parallel.world_size() if parallel.active() else 1.0)
 
 
+@MORE_LOSS_HEADS_REGISTRY.register()
+class SoftCELossHead(CELossHead):
+    """Similarity-weighted InfoNCE (continuously weighted contrastive learning, CWCL; SoftCLIP and ALBEF's momentum targets are the
+    same family): the soft-max target of row i is spread over the batch by W_ij = clamp((c_ij - w_floor) / (1 - w_floor), 0, 1) ^
+    w_power, W_ii = 1, where c is the pairwise cosine similarity of a frozen "teacher" modality -- what batches of near-duplicate
+    frames or paraphrased captions need, whose false negatives carry no label id.  Config keys: `teacher` = x2 | x1 (the head's own
+    normalised operand, detached: the frozen tower's side of the pair) | given (a `teacher=` keyword tensor [b, Et], normalised and
+    detached here); `w_floor` (-1: CWCL's (1 + c) / 2), `w_power`.  One fused call (ops.SoftNCEFn); under replicas with global
+    negatives the teacher rows are gathered with the features, without gradient, and a rank takes its strip, as CELossHead does.
+    Evaluation (`infer`, `report`) is CELossHead's."""
+
+    def __init__(self, cfg, teacher=None, **kwargs):
+        super().__init__(cfg, **kwargs)
+        self.teacher = str(teacher if teacher is not None else getattr(cfg, "teacher", "x2"))
+        self.w_floor, self.w_power = float(getattr(cfg, "w_floor", -1.0)), float(getattr(cfg, "w_power", 1.0))
+        if self.teacher not in ("x1", "x2", "given"):
+            raise VipantError(f"model.loss.teacher={self.teacher}: one of x1, x2, given")
+        if not -1.0 <= self.w_floor < 1.0:
+            raise VipantError(f"model.loss.w_floor={self.w_floor}: need -1 <= w_floor < 1 (the similarity at which a pair's weight reaches 0)")
+        if not self.w_power > 0.0:
+            raise VipantError(f"model.loss.w_power={self.w_power}: need w_power > 0")
+
+    def describe(self):
+        return f"soft positives: teacher {self.teacher}, w_floor {self.w_floor:g}, w_power {self.w_power:g}"
+
+    def forward(self, x1, x2, *args, teacher=None, **kwargs):
+        if not self.training:
+            return super().forward(x1, x2, *args, **kwargs)
+        if not kwargs.get("normalized", False):
+            x1, x2 = ops.L2NormFn.apply(x1), ops.L2NormFn.apply(x2)
+        if self.teacher == "given":
+            if teacher is None:
+                raise VipantError("SoftCELossHead with teacher=given needs the `teacher=` rows of the batch")
+            with torch.no_grad():
+                t = ops.L2NormFn.apply(teacher.detach().float())
+        scale_max = 0.0 if self.scale_max == float("inf") else float(self.scale_max)
+        ls = self.logit_scale if isinstance(self.logit_scale, nn.Parameter) else self.logit_scale.to(x1.device)
+        b = x1.shape[0]
+        if parallel.active() and self.negatives == "global":
+            x1g, x2g = parallel.all_gather_features(x1, x2)
+            tg = parallel.all_gather_features(t)[0] if self.teacher == "given" else (x1g if self.teacher == "x1" else x2g).detach()
+            return ops.SoftNCEFn.apply(x1g, x2g, tg, self.w_floor, self.w_power, ls, scale_max, parallel.rank() * b, b, 1.0)
+        if self.teacher != "given":
+            x1, x2 = x1.contiguous(), x2.contiguous()
+            t = (x1 if self.teacher == "x1" else x2).detach()        # the operand's own memory: the call shares its copies
+        return ops.SoftNCEFn.apply(x1, x2, t, self.w_floor, self.w_power, ls, scale_max, 0, b,
+                                   1.0 / parallel.world_size() if parallel.active() else 1.0)
+
+
 @LOSS_HEADS_REGISTRY.register()
 class VALCELossHead(LossHead):
     """Sum of pairwise InfoNCE heads over {vision, audio, language} (loss_head.py:421-495); the AT script
     enables only `al`.  Optional key `label_positives`: the pairs among `va`, `lv`, `al` that are LabelCELossHeads and receive the
-    batch's `groups`; absent, every pair is a CELossHead."""
+    batch's `groups`; optional key `soft_positives`: a mapping from pair to teaching operand (x1 | x2 of that pair, e.g. {va: x1,
+    al: x2}: the image teaches the VA pair, the text the AL pair), whose pairs are SoftCELossHeads; absent, every pair is a CELossHead."""
 
     def __init__(self, cfg, **kwargs):
         super().__init__()
@@ -300,8 +350,17 @@ class VALCELossHead(LossHead):
         labelled = [str(k) for k in (getattr(cfg, "label_positives", None) or [])]
         if any(k not in ("va", "lv", "al") for k in labelled):
             raise VipantError(f"model.loss.label_positives={labelled}: a list drawn from va, lv, al")
+        soft = {str(k): str(v) for k, v in dict(getattr(cfg, "soft_positives", None) or {}).items()}
+        if any(k not in ("va", "lv", "al") or v not in ("x1", "x2") for k, v in soft.items()):
+            raise VipantError(f"model.loss.soft_positives={soft}: a mapping from va, lv, al to the teaching operand x1 or x2")
+        if set(soft) & set(labelled):
+            raise VipantError(f"model.loss: {sorted(set(soft) & set(labelled))} listed in both label_positives and soft_positives")
         self.wants_groups = bool(labelled)
-        pair = lambda key: (LabelCELossHead if key in labelled else CELossHead)(cfg, **kwargs)
+
+        def pair(key):
+            if key in soft:
+                return SoftCELossHead(cfg, teacher=soft[key], **kwargs)
+            return (LabelCELossHead if key in labelled else CELossHead)(cfg, **kwargs)
         if cfg.va:
             self.loss_head_va = pair("va")
             self._total_loss.update({"va": 0.})
@@ -314,6 +373,10 @@ class VALCELossHead(LossHead):
 
     def copy_state_dict(self, state_dict):
         pass
+
+    def describe(self):
+        heads = (("va", self.loss_head_va), ("lv", self.loss_head_lv), ("al", self.loss_head_al))
+        return "; ".join(f"{key}: {head.describe()}" for key, head in heads if isinstance(head, SoftCELossHead))
 
     def _pairs(self, x1, x2, x3):
         return (("va", self.loss_head_va, x1, x2), ("lv", self.loss_head_lv, x1, x3), ("al", self.loss_head_al, x2, x3))

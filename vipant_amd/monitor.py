@@ -161,6 +161,9 @@ class Monitor(object):
         self.build_optimizer(tunable_params)
         if getattr(model.loss_head, "wants_groups", False) and not self.label_groups:
             self.echo("The loss head takes label positives, but these batches carry no label ids: it runs with identity positives.")
+        described = getattr(model.loss_head, "describe", None)      # SoftCELossHead, VALCELossHead with `soft_positives`
+        if described is not None and described():
+            self.echo(f"The loss head takes {described()}.")
 
     def _configure(self, model):
         """Run-time switches of the towers (`running.*`) and, under replicas, the gradient reduction they feed."""

@@ -1383,6 +1383,54 @@ class LabelNCEFn(torch.autograd.Function):
         return (g1, g2, None, gls, None, None, None, None)
 
 
+class SoftNCEFn(torch.autograd.Function):
+    """Similarity-weighted InfoNCE (SoftCELossHead.forward) on L2-normalised fp32 features: the soft-max target of row i is spread
+    over the batch by W_ij = clamp((<t_i, t_j> - w_floor) / (1 - w_floor), 0, 1) ^ w_power, W_ii = 1 (vipant_soft_nce_fwd_bwd,
+    include/vipant_hip.h).
+
+    x1, x2: [B, E] -- the (all-gathered) global batch; teacher: fp32 [B, Et] L2-normalised rows, a constant (it gets no gradient; a view of the
+    memory of x1 or x2, such as `x2.detach()`, is recognised by its address and shares that operand's copies) or None (W = I: InfoNCEFn's loss).  Strip and
+    `grad_scale` conventions are InfoNCEFn's: full-batch loss and `logit_scale` gradient on every caller, feature gradients for rows
+    [row0, row0 + nrows)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, teacher, w_floor, w_power, logit_scale, scale_max, row0, nrows, grad_scale):
+        _need(x1, F32, "soft_nce.x1"); _need(x2, F32, "soft_nce.x2")
+        x1, x2 = x1.contiguous(), x2.contiguous()
+        B, E = x1.shape
+        dev = x1.device
+        Et = 0
+        if teacher is not None:
+            teacher = teacher.detach()
+            _need(teacher, F32, "soft_nce.teacher")
+            if teacher.dim() != 2 or teacher.shape[0] != B:
+                raise _ffi.VipantError(f"soft_nce.teacher: need {B} rows, got {tuple(teacher.shape)}")
+            teacher = teacher.contiguous()
+            Et = teacher.shape[1]
+        need = ctx.needs_input_grad
+        want = need[0] or need[1] or need[5]
+        nbytes = query("vipant_soft_nce_workspace_bytes", B, E, Et, int(nrows))
+        ws = scratch("soft_nce", max(nbytes, 256), dev)
+        loss = torch.empty((1,), dtype=F32, device=dev)
+        d1 = torch.empty((nrows, E), dtype=F32, device=dev) if want else None
+        d2 = torch.empty((nrows, E), dtype=F32, device=dev) if want else None
+        dls = torch.empty((1,), dtype=F32, device=dev) if want else None
+        ls = logit_scale.detach().reshape(1).to(F32)
+        call("vipant_soft_nce_fwd_bwd", x1.data_ptr(), x2.data_ptr(), _ptr(teacher), Et, float(w_floor), float(w_power), ls.data_ptr(),
+             float(scale_max or 0.0), loss.data_ptr(), _ptr(d1), _ptr(d2), _ptr(dls), float(grad_scale), B, E, int(row0), int(nrows),
+             ws.data_ptr(), nbytes, _stream())
+        if want:
+            ctx.save_for_backward(d1, d2, dls)
+            ctx.meta = (B, E, int(row0), int(nrows), tuple(logit_scale.shape))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        need = ctx.needs_input_grad
+        g1, g2, gls = _nce_backward(ctx, dloss, (need[0], need[1], need[5]))
+        return (g1, g2, None, None, None, gls, None, None, None, None)
+
+
 class SigmoidLossFn(torch.autograd.Function):
     """Pairwise sigmoid contrastive loss (SigmoidLossHead.forward) on L2-normalised fp32 features: one fused call
     (vipant_sigmoid_loss_fwd_bwd) in the forward, which leaves every gradient; the backward scales them.
