@@ -663,6 +663,49 @@ int32_t vipant_pcm_ingest(const uint8_t* raw, int64_t byte_stride, const int64_t
                           int32_t mode, const int64_t* tile_len, float* wave, int64_t wave_stride, int64_t* nsamples_out, int64_t b,
                           void* stream);
 
+/* ---- sample-rate conversion (vipant_amd/csrc/resample.hip): every clip of a batch to one rate, between the ingest and the log-mel ----
+ * The reference has no such stage (it takes each file at its own rate, cvap/data/audio/transform.py:15-35); this replaces what audio
+ * pipelines do per file on the host with torchaudio.functional.resample(waveform, orig, new, lowpass_filter_width, rolloff), the Hann-
+ * windowed sinc (resampling_method "sinc_interp_hann"), and an offline single-rate copy of the dataset.  With g = gcd(orig, new),
+ * o = orig / g, n = new / g, base = min(o, n) * rolloff, L = lowpass_filter_width, w = ceil(L o / base), for phase j < n, tap k < 2w + o:
+ *   t = clamp((-j / n + (k - w) / o) * base, -L, L);   K[j,k] = (t == 0 ? 1 : sin(pi t) / (pi t)) * cos^2(pi t / (2 L)) * base / o
+ *   out[i n + j] = sum_k K[j,k] x[i o + k - w]   (x = 0 outside [0, len)),   len_out = ceil(n len / o)
+ * K in fp64, rounded once to fp32; the taps with |t| >= L before the clamp are exactly 0 in fp32 and are dropped: per phase the table
+ * keeps T taps from k0[j] on.  The sum is one fp32 FMA per tap in ascending k from +0: the same bits on every run, in any batch.
+ *
+ * vipant_resample_plan: host only, no device call.  Fills *cls for the pair -- everything but `table` -- or refuses the pair with
+ * VIPANT_EBADSHAPE and a message that names it and the bytes it needs: more than 65535 phases or taps per phase, or a table plus one
+ * period's input span beyond the 160 KB of a workgroup's LDS (44101 -> 16000: 16000 phases).  orig == new gives the identity class
+ * (T = 0, no table): a copy, bit for bit.  P = the periods a workgroup owns (P n outputs, at most 4096; a multiple of 4 unless only
+ * 3, 2 or 1 fit), kmin = min k0, kspan = max k0 - min k0 + T, lds_bytes = table and span of one workgroup. */
+#define VIPANT_RESAMPLE_MAX_CLASSES 16
+typedef struct vipant_resample_class {
+    const void* table;          /* device, 16-byte aligned: coef fp32 [T][n], then k0 int32 [n] (vipant_resample_table); NULL for T = 0 */
+    int32_t orig, fresh;        /* the pair, in Hz */
+    int32_t o, n, T, w, P, kmin, kspan, lds_bytes;
+} vipant_resample_class;
+int32_t vipant_resample_plan(int64_t orig, int64_t fresh, int32_t lowpass_filter_width, double rolloff, vipant_resample_class* cls);
+/* The size of a pair's table, (T + 1) n 4 bytes; 0 for the identity class and for a pair the plan refuses. */
+size_t vipant_resample_table_bytes(int64_t orig, int64_t fresh, int32_t lowpass_filter_width, double rolloff);
+/* Builds a pair's table on the device in one launch (replaces torchaudio's _get_sinc_resample_kernel, which builds the dense
+ * [n, 2w + o] kernel with torch ops per call): fp64 arithmetic, one rounding to fp32, transposed so that lanes owning consecutive
+ * phases read consecutive words.  The host computes no coefficient and waits for nothing.  Refused, nothing written: a pair the plan
+ * refuses; VIPANT_EALIGN for a NULL or unaligned table; VIPANT_ENOWORKSPACE for `bytes` below vipant_resample_table_bytes. */
+int32_t vipant_resample_table(int64_t orig, int64_t fresh, int32_t lowpass_filter_width, double rolloff, void* table, size_t bytes,
+                              void* stream);
+/* The conversion itself, for clips of any mix of classes (replaces one torchaudio.functional.resample call -- a strided conv1d over the
+ * dense kernel -- per file): wave fp32 [b, wave_stride] and nsamples int64 [b] on the device, out fp32 [b, out_stride] and
+ * nsamples_out int64 [b] on the device.  cls int32 [b] and classes [nclasses] are HOST arrays, as the caller grouped its clips by rate
+ * on the host: clip i has class classes[cls[i]], a descriptor of vipant_resample_plan with its `table` set.  Both travel in the
+ * launch's argument block (2048 clips per launch): no copy, no wait, and the call may be captured into a graph.  nsamples[i] is clamped
+ * into [0, wave_stride]; nothing of a row past it is read (the padding may hold anything).  Every element of [b, out_stride] is
+ * written exactly once: the clip's len_out outputs (clamped to out_stride), then zeros; nsamples_out[i] = that length.
+ * Refused with VIPANT_EBADSHAPE before any launch, nothing written: a NULL argument, b < 1, a stride < 1, nclasses outside [1, 16], out
+ * overlapping wave, a descriptor that is no plan's or lacks its table, a cls[i] outside [0, nclasses).  No workspace, no atomics. */
+int32_t vipant_resample(const float* wave, int64_t wave_stride, const int64_t* nsamples, const int32_t* cls,
+                        const vipant_resample_class* classes, int32_t nclasses, float* out, int64_t out_stride, int64_t* nsamples_out,
+                        int64_t b, void* stream);
+
 /* ---- log-mel ingest (vipant_amd/csrc/logmel.hip): stored log-mels of the npz datasets -> the towers' fp32 input ----
  * What the reference's three npz dataset classes do per item on the host in numpy, for a ragged batch in one launch.  raw uint8
  * [b, byte_stride] on the device: clip i = nframes[i] rows of F little-endian elements of format fmt[i], C-contiguous, zero padded;

@@ -65,6 +65,15 @@ class FbankCall(C.Structure):
                 ("nfft", _i32), ("zero_mean", _i32), ("preemphasis", _f32), ("norm_mean", _f32), ("norm_std", _f32), ("reserved", _i32)]
 
 
+RESAMPLE_MAX_CLASSES = 16                                                            # VIPANT_RESAMPLE_MAX_CLASSES
+
+
+class ResampleClass(C.Structure):
+    """struct vipant_resample_class (include/vipant_hip.h): one rate pair's plan and table, as vipant_resample reads it."""
+    _fields_ = [("table", _p), ("orig", _i32), ("fresh", _i32), ("o", _i32), ("n", _i32), ("T", _i32), ("w", _i32), ("P", _i32),
+                ("kmin", _i32), ("kspan", _i32), ("lds_bytes", _i32)]
+
+
 class ImageParams(C.Structure):
     """struct vipant_image_params (include/vipant_hip.h): the static parameters of vipant_image_view, by value."""
     _fields_ = [("n", _i32), ("mean", _f32 * 3), ("std", _f32 * 3), ("chain", _i32)]
@@ -151,6 +160,10 @@ PROTOTYPES = {
     "vipant_wave_view": (_i32, [_p, _i64, _p, _p, _i64, _p, _i64, ViewParams, _p, _p, _sz, _p]),
     "vipant_pcm_wave": (_i32, [_p, _i64, _p, _p, _i32, _i64, _p, _i64, _p, _i64, _p]),
     "vipant_pcm_ingest": (_i32, [_p, _i64, _p, _p, _p, _i32, _p, _p, _i64, _p, _i64, _p]),
+    "vipant_resample_plan": (_i32, [_i64, _i64, _i32, _f64, C.POINTER(ResampleClass)]),
+    "vipant_resample_table_bytes": (_sz, [_i64, _i64, _i32, _f64]),
+    "vipant_resample_table": (_i32, [_i64, _i64, _i32, _f64, _p, _sz, _p]),
+    "vipant_resample": (_i32, [_p, _i64, _p, _p, C.POINTER(ResampleClass), _i32, _p, _i64, _p, _i64, _p]),
     "vipant_logmel_ingest": (_i32, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _f32, _i32, _p]),
     "vipant_fbank_rows_workspace_bytes": (_sz, [_i64]),
     "vipant_fbank_rows": (_i32, [C.POINTER(FbankCall), _p]),

@@ -2,13 +2,15 @@
 `AudioBatches` is built from `running.audio`, the device and a per-rank seed and knows no model: whether training is on is an argument
 of every call.  One method per batch the reference's datasets make, each for a PcmBatch (one sample rate: `pcm_wave`, `KaldiFbank`)
 and a RawPcmBatch (`running.audio.native_pcm`: `pcm_ingest`, `RateFbank`) alike, and each the one place that states the order of its
-host draws -- a parity contract with the reference that the trainer tests replay from an identically seeded generator."""
+host draws -- a parity contract with the reference that the trainer tests replay from an identically seeded generator.
+With `running.audio.resample_to` (a rate in Hz; 0 = off) every method brings its clips to that rate first (`frontend.Resample`, one
+launch per batch, mixup partners included) and runs the `KaldiFbank` of that rate: crop length, masks and views live there."""
 from __future__ import annotations
 
 import torch
 
 from . import frontend
-from .frontend import KaldiFbank, LogmelIngest, RateFbank
+from .frontend import KaldiFbank, LogmelIngest, RateFbank, Resample
 
 # FbankTransform's own normalisation (cvap/data/audio/transform.py:228-229, :238-239, :247-248): the siamese dataset does not read
 # `running.audio.norms`
@@ -60,10 +62,27 @@ class AudioBatches:
         return LogmelIngest.from_config(acfg, train=train, dataset_kind=kind, device=self.device)
 
     def _waves(self, kind, clips, train, mode="first", tile=False):
-        """-> (the front-end of the clips' batch type, the positional arguments of its call, the host lengths, the rates or None)."""
-        fbank = self.frontend(kind, train, getattr(clips, "sample_rate", None))
+        """-> (the front-end of the clips' batch type, the positional arguments of its call, the host lengths, the rates or None).
+        With `running.audio.resample_to`: the waveform as without it -- a clip is tiled at its own rate --, then all rows to that
+        rate (skipped for a PcmBatch already there); the front-end is that rate's, the lengths are the new ones, the rates None."""
+        to = int(self.acfg.get("resample_to", 0) or 0)
+        fbank = self.frontend(kind, train, to if to else getattr(clips, "sample_rate", None))
         wave, nsamples, n, rates = frontend.clip_waves(clips, self.device, mode, fbank.max_len / 100 if tile else 0.0)
+        if to:
+            source = rates if rates is not None else clips.sample_rate
+            if rates is not None or int(source) != to:
+                resample = self.resampler(to)
+                wave, nsamples = resample(wave, nsamples, source, host_lengths=n)
+                n = resample.lengths(n, source)
+            return fbank, (wave, nsamples), n, None
         return fbank, (wave, nsamples) if rates is None else (wave, nsamples, rates), n, rates
+
+    def resampler(self, rate):
+        """The `Resample` to `rate`, built on first use (it keeps the tables of the source rates it has seen)."""
+        key = ("resample", int(rate))
+        if key not in self._frontends:
+            self._frontends[key] = Resample(int(rate), device=self.device)
+        return self._frontends[key]
 
     def single_view(self, clips, train: bool, tile=None):
         """A PcmBatch / RawPcmBatch -> log-mels, in the reference's order (image_audio.py:183-207, transform.py:15-35): H2D, the
@@ -107,7 +126,7 @@ class AudioBatches:
         """The clips of a raw-file tagging batch -- b clips and, behind them, the partner clips the loader's workers drew
         (audioset_cls.py:374-400) -- and mix = (index, lambda) with b rows -> b log-mels: the waveform of all rows (channel 0, never
         tiled -- `wf[:1]`), then one launch that mixes and writes b rows.  The waveform is always zero-mean (:377), a longer clip is
-        cut at `max_len` frames (:410); a partner of any rate is added sample by sample.
+        cut at `max_len` frames (:410); a partner of any rate is added sample by sample (under `resample_to` it has the batch's rate).
         Draws: training -- `draw_masks(b)` for the b outputs; evaluation -- none."""
         fbank, args, _, _ = self._waves("config", clips, train)
         b = int(mix[0].shape[0])

@@ -41,6 +41,8 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-re
 # item walk of dpos; both wait on memory).
 # lamb.hip: new code, built without the packed forms (its passes wait on memory: 16 to 24 bytes per element against a few dozen
 # scalar-per-lane operations).
+# resample.hip: new code, built without the packed forms (its inner loop is four scalar FMAs per coefficient against LDS reads of
+# unrelated addresses; nothing pairs up).
 # (The feature belongs to the device pass; the host pass of the same command reports it as unknown and ignores it.)
 EXTRA_CFLAGS = {"gemm_nt.hip": ["-mllvm", "-disable-machine-sink", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm"],
                 "layernorm_widths.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
@@ -49,7 +51,8 @@ EXTRA_CFLAGS = {"gemm_nt.hip": ["-mllvm", "-disable-machine-sink", "-mllvm", "-a
                 "soft_nce.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "hinge.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "patch_keep.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-                "lamb.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                "lamb.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                "resample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 # files whose device assembly is kept beside the object (lib/obj/<name>-hip-amdgcn-amd-amdhsa-gfx950.s): kernels with hand-counted

@@ -91,6 +91,9 @@ GROUPS = {
             # read a WAV file's samples as shipped (8 / 16 / 24 / 32-bit PCM, 32-bit float, extensible headers) and compute each clip's
             # log-mel at the file's own sample rate, as the reference does; off: 16-bit, one rate, as before
             "native_pcm": False,
+            # bring every clip to this sample rate on the device before the log-mel (`frontend.Resample`: the windowed sinc of
+            # torchaudio.functional.resample), so that a tower sees the mel axis its checkpoint was trained on; 0: off
+            "resample_to": 0,
         },
     },
     "model/image": {

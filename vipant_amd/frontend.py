@@ -6,12 +6,15 @@ SpecAugment masks (image_audio.py:183-207, configs/running/audio/default.yaml). 
 batch of device-resident waveforms in two launches (`vipant_fbank`; three with waveform mixup, `vipant_fbank_mix`) and returns the [b, 1, T, F] tensor
 `ViTPreEncoder` takes.  With `outputs=b` the mixup partners may be rows of `wave` past the b clips of the batch (`vipant_fbank_mix_src`):
 the file loader draws a partner from the whole dataset and ships its clip behind the batch; such a row is read, never written.  File decoding stays with the loader (vipant_amd/data); `pcm_wave` turns the 16-bit PCM it decodes into
-those waveforms in one launch (`vipant_pcm_wave`: int16 -> fp32, the channel rule, `tile_audio`).  There is no resampling.
+those waveforms in one launch (`vipant_pcm_wave`: int16 -> fp32, the channel rule, `tile_audio`).  On this path there is no resampling:
+a dataset has one rate.
 
 Under `running.audio.native_pcm` the loader ships the samples as the files hold them and every clip keeps its own sample rate, as in
 the reference (torchaudio.load normalises any width, kaldi.fbank is called with the file's rate): `pcm_ingest` converts 8 / 16 / 24 /
 32-bit PCM and 32-bit float on the device (`vipant_pcm_ingest`), and `RateFbank` groups a batch by rate and runs one
-`vipant_fbank_rows` call per rate class over a list of rows, at padded sizes 256 .. 8192.  Still no resampling.
+`vipant_fbank_rows` call per rate class over a list of rows, at padded sizes 256 .. 8192.  With
+`running.audio.resample_to` the clips are brought to that one rate first, on the device (`Resample`: `vipant_resample`, the windowed
+sinc of torchaudio.functional.resample), and the filter bank is the `KaldiFbank` of that rate.
 The two filter banks share a base, `Fbank`: the settings read from `running.audio` (`fbank_config`), the host draws, the argument
 rules of `__call__` and the view plan; each says its `crop_len_for(rate)`.  `clip_waves` is the one ingest door of the trainers, for a
 PcmBatch and a RawPcmBatch alike; the host's copy of the lengths comes from `pcm_lengths` / `raw_lengths`.  What the trainers make of
@@ -234,6 +237,87 @@ def clip_waves(clips, device, mode: str = "first", tile_secs: float = 0.0):
     wave, nsamples = pcm_wave(on_dev.pcm, on_dev.nframes, on_dev.channels, mode=mode, tile_len=tile_len,
                               wave_stride=max(8, -(-int(n.max()) // 8) * 8))
     return wave, nsamples, n, None
+
+
+class Resample:
+    """Every clip of a batch to `target_rate`, on the device, in one launch (`vipant_resample`; `running.audio.resample_to`): the
+    band-limited polyphase interpolation of torchaudio.functional.resample(waveform, rate, target_rate, lowpass_filter_width,
+    rolloff) with its Hann-windowed sinc.  A rate pair is a class: its plan comes from the host
+    (`vipant_resample_plan`; a pair whose table does not fit a workgroup's LDS, such as 44101 -> 16000, is refused there, when the
+    object first sees the rate and before any launch), its table is built on the device when the pair first runs
+    (`vipant_resample_table`) and kept.  A clip already at the target rate is copied bit for bit."""
+
+    def __init__(self, target_rate: int, lowpass_filter_width: int = 6, rolloff: float = 0.99, device="cuda:0"):
+        self.target_rate, self.width, self.rolloff = int(target_rate), int(lowpass_filter_width), float(rolloff)
+        self.device = torch.device(device)
+        if self.target_rate < 1:
+            raise VipantError(f"resample: target rate {target_rate} Hz")
+        self._plans, self._tables = {}, {}
+
+    def plan(self, rate) -> "_ffi.ResampleClass":
+        """The class descriptor of rate -> target_rate, without its table: o, n, T, w, P (the periods a workgroup owns: P n outputs
+        from (P - 1) o + kspan inputs), kmin, kspan, lds_bytes.  Host only; raises for a pair the kernels refuse."""
+        rate = int(rate)
+        if rate not in self._plans:
+            c = _ffi.ResampleClass()
+            call("vipant_resample_plan", rate, self.target_rate, self.width, self.rolloff, _ffi.C.byref(c))
+            self._plans[rate] = c
+        return self._plans[rate]
+
+    def _class(self, rate):
+        rate, c = int(rate), self.plan(rate)
+        if c.T and rate not in self._tables:
+            nbytes = query("vipant_resample_table_bytes", rate, self.target_rate, self.width, self.rolloff)
+            table = torch.empty(nbytes // 4, dtype=F32, device=self.device)
+            call("vipant_resample_table", rate, self.target_rate, self.width, self.rolloff, table.data_ptr(), nbytes, ops._stream())
+            self._tables[rate] = table
+            c.table = table.data_ptr()
+        return c
+
+    def lengths(self, n, rates):
+        """The lengths `__call__` will report, ceil(n_class * len / o_class), from the host's copies in Python integers (no device
+        sync) -> int64 [b].  rates: one per row, or one for the batch."""
+        n = torch.as_tensor(n).reshape(-1).tolist()
+        rates = self._rates(rates, len(n))
+        return torch.tensor([-(-self.plan(r).n * max(int(k), 0) // self.plan(r).o) for k, r in zip(n, rates)], dtype=torch.int64)
+
+    @staticmethod
+    def _rates(rates, b):
+        rates = torch.as_tensor(rates).reshape(-1).tolist()
+        if len(rates) == 1:
+            rates = rates * b
+        if len(rates) != b:
+            raise VipantError(f"resample: {len(rates)} rates for {b} rows")
+        return [int(r) for r in rates]
+
+    def __call__(self, wave: torch.Tensor, nsamples: torch.Tensor, rates, host_lengths=None):
+        """wave fp32 [b, stride] on the device, nsamples int64 [b] on the device, rates: host integers, one per row or one for the
+        batch -> (wave_out fp32 [b, out_stride], zero beyond a clip's length; nsamples_out int64 [b]).  host_lengths: the host's copy
+        of nsamples (as `clip_waves` returns it): out_stride is then the longest new length rounded up to 8; without it, the longest
+        a row of `stride` samples can become.  Nothing here synchronises with the device."""
+        if not isinstance(wave, torch.Tensor) or not wave.is_cuda or wave.dtype != F32 or wave.dim() != 2:
+            raise VipantError("resample: wave must be a 2-d float32 device tensor (there is no CPU path)")
+        wave = wave.contiguous()
+        b, stride = wave.shape
+        rates = self._rates(rates, b)
+        groups = RateFbank.group(rates)
+        if len(groups) > _ffi.RESAMPLE_MAX_CLASSES:
+            raise VipantError(f"resample: a batch with {len(groups)} sample rates; one launch takes {_ffi.RESAMPLE_MAX_CLASSES}")
+        classes = (_ffi.ResampleClass * len(groups))(*[self._class(rate) for rate, _ in groups])     # every refusal before the launch
+        cls = (_ffi.C.c_int32 * b)()
+        for k, (_, members) in enumerate(groups):
+            for i in members:
+                cls[i] = k
+        longest = self.lengths(host_lengths if host_lengths is not None else [stride] * b, rates)
+        out_stride = max(8, -(-int(longest.max()) // 8) * 8)
+        nsamples = nsamples.to(device=wave.device, dtype=torch.int64).contiguous()
+        if nsamples.shape != (b,):
+            raise VipantError(f"resample: nsamples must have shape [{b}], got {tuple(nsamples.shape)}")
+        out = torch.empty((b, out_stride), dtype=F32, device=wave.device)
+        nout = torch.empty((b,), dtype=torch.int64, device=wave.device)
+        call("vipant_resample", wave.data_ptr(), stride, nsamples.data_ptr(), cls, classes, len(groups), out.data_ptr(), out_stride,
+             nout.data_ptr(), b, ops._stream())
+        return out, nout
 
 
 def fbank_config(acfg, train: bool = True) -> dict:
